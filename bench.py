@@ -6,7 +6,13 @@ whole hot path over one batch already resident in HBM: mel/energy, Praat-AC F0, 
 Whisper log-mel + encoder, content map, conditioner, PLMS-100 sampler, de-normalisation, BigVGAN,
 fade-out, and (N > 1) the RCCL gather of every rank's waveforms to rank 0.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs the W warmup steps, times the K steps, writes the last timed step's outputs (--dump-outputs)
+and prints the result line with the headline figure alone. `--full` adds everything else the benchmark measures, each
+in untimed steps of its own around the same timed region: the per-kernel breakdown (one profiled warmup step), the
+dominant kernel's roofline (one profiled step after the timed ones, and a single-stream pass), the GPU clocks sampled
+through the timed region, the box-speed calibration GEMM / copy, and the CPU baseline (the oracle on one clip).
 
 N > 1: either launched by torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE set, one process per GPU), or, when
 WORLD_SIZE is unset, this process spawns the N ranks itself (spawn_ranks) BEFORE anything touches the GPU and exits
@@ -57,6 +63,25 @@ def synth_inputs(uids, seconds, float16k=False):
     else:
         w16 = np.stack([synth_clip_16k_quantised(int(u), seconds) for u in uids])
     return w24, w16
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: save {name: array} as dirname/<name>.npy, float64 where the path computes float64 and float32
+    otherwise. All arrays together stay within DUMP_BUDGET_BYTES: when they would not, each is cut to its proportional
+    share, a fixed sample (generator seed 0, sorted flat indices, so the same elements in every run and build) saved
+    as a 1-D array."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * (DUMP_BUDGET_BYTES / total)))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, keep))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def host_cpus():
@@ -355,11 +380,14 @@ def dry_run(args, dist):
         assert out.shape[0] == dist.world * B and bool(torch.isfinite(out).all())
         if args.dump:
             np.save(args.dump, out.numpy())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"wav": out.numpy()})
         print(json.dumps({"metric": "dry-run gather (identity conversion, CPU)", "n_gpus": args.gpus,
                           "dist_world": dist.world, "backend": dist.backend or "none",
                           "rccl_world": torchdist.get_world_size() if torchdist.is_initialized() else 1,
                           "gather_ms_per_step": [round(v, 3) for v in gather_ms], "steps": args.steps,
                           "per_rank_s": [round(t, 4) for t in per_rank], "elapsed_s": round(elapsed, 4),
+                          "ms_per_step": round(1000.0 * elapsed / args.steps, 3),
                           "gathered": list(out.shape), "lengths": lens.tolist()}), flush=True)
     dist.close()
 
@@ -377,17 +405,25 @@ def main():
                     help="collective timeout in seconds (default SVC_DIST_TIMEOUT_S or 600)")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save what the last timed step returned (rank 0: the gathered "
+                         "waveforms `wav` and its own `mel`, `f0`, `x0`) as DIR/<name>.npy, float32 / float64, at most "
+                         "64 MB in all (a fixed seeded sample of each array when they are larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need, in untimed steps of their own: "
+                         "per-kernel breakdown, roofline of the dominant kernel, GPU clocks, box-speed calibration, "
+                         "CPU baseline (the --no-* options below switch single parts of it off)")
     ap.add_argument("--batch", type=int, default=32, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=10.0)
     ap.add_argument("--speedup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-calib", action="store_true", help="skip the box-speed calibration GEMM / copy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-calib", action="store_true", help="(--full) skip the box-speed calibration GEMM / copy")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads for the CPU baseline (default: every CPU available to the process)")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "pmc_traffic.json"))
     ap.add_argument("--no-isolated-pass", action="store_true",
-                    help="skip the untimed single-stream pass of the dominant call site (profiling runs: every launch "
-                         "of the dominant kernel in the trace is then a production launch)")
+                    help="(--full) skip the untimed single-stream pass of the dominant call site (profiling runs: "
+                         "every launch of the dominant kernel in the trace is then a production launch)")
     ap.add_argument("--content", choices=["whisper", "contentvec"], default="whisper",
                     help="content encoder (BASELINE config 5: contentvec = the HuBERT/ContentVec variant)")
     ap.add_argument("--sampler", choices=["plms", "ddpm"], default="plms",
@@ -404,6 +440,8 @@ def main():
                     help="wsplit: bit mask of the Whisper blocks whose MLP linears are weight-split (default 0xf; "
                          "16777215 = all 24, the round-2 default before the precision sweep)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -452,15 +490,15 @@ def main():
         out = dist.gather_waveforms(res.wav)
         torch.cuda.synchronize()
         gather_s.append(time.perf_counter() - tg)
-        return out
+        return out, res
 
-    # Warmup. The last warmup step runs with every launch profiled (HIP events around each kernel): that
-    # gives the per-kernel breakdown and picks the dominant kernel. The timed steps then record events
-    # only around that kernel's launches (svc_profile_filter), so the roofline is measured live in the
-    # timed region without bracketing the other ~4 000 launches per step.
+    # Warmup. With --full (which needs at least one warmup step) the last warmup step runs with every launch profiled
+    # (HIP events around each kernel): that gives the per-kernel breakdown and picks the dominant kernel, whose
+    # roofline figures come from profiled steps of their own after the timed region.
     prof_all = {}
-    for i in range(max(args.warmup, 1)):
-        last = i == max(args.warmup, 1) - 1
+    n_warmup = max(args.warmup, 1) if args.full else args.warmup
+    for i in range(n_warmup):
+        last = args.full and i == n_warmup - 1
         if last:
             _lib.profile_enable(True)
         step()
@@ -470,57 +508,100 @@ def main():
             _lib.profile_enable(False)
         log(f"warmup {i + 1}/{args.warmup}")
 
-    by_kernel = family(prof_all)
-    dom_name = max(by_kernel.items(), key=lambda kv: kv[1]["ms"])[0]
-    share = by_kernel[dom_name]["ms"] / sum(v["ms"] for v in by_kernel.values())
-    dom_site = max((n for n in prof_all if n.split("@")[0] == dom_name), key=lambda n: prof_all[n]["ms"])
-    dom_site = dom_site.split("@")[1] if "@" in dom_site else ""
-
-    # The sampler runs utterance-aligned sub-batches on concurrent streams (kernel switch sampler_streams, read back
-    # from the library), so a launch's HIP-event duration includes time shared with the other streams' kernels. One
-    # extra untimed step with the sampler on a single stream gives the dominant call site's isolated per-launch rate.
-    streams = int(eng.get_config("tune.sampler_streams"))
     isolated = None
-    if streams > 1 and dom_site.startswith("diffsvc.") and not args.no_isolated_pass:
-        eng.tune(sampler_streams=1)
-        _lib.profile_enable(True)
-        step()
-        torch.cuda.synchronize()
-        iso = _lib.profile_read()
-        _lib.profile_enable(False)
-        eng.tune(sampler_streams=streams)
-        at_site = {n.split("@")[0]: v for n, v in iso.items() if n.endswith("@" + dom_site)}
-        if at_site:
-            k, v = max(at_site.items(), key=lambda kv: kv[1]["ms"])
-            us = v["ms"] * 1000.0 / v["launches"]
-            tf = v["flops"] / v["launches"] / (us * 1e-6) / 1e12
-            isolated = {"kernel": k, "site": dom_site, "avg_launch_us": round(us, 2), "achieved": round(tf, 2),
-                        "frac": round(tf / PEAK_F16_TFLOPS, 4), "sampler_streams": 1, "launches": v["launches"]}
+    if args.full:
+        by_kernel = family(prof_all)
+        dom_name = max(by_kernel.items(), key=lambda kv: kv[1]["ms"])[0]
+        share = by_kernel[dom_name]["ms"] / sum(v["ms"] for v in by_kernel.values())
+        dom_site = max((n for n in prof_all if n.split("@")[0] == dom_name), key=lambda n: prof_all[n]["ms"])
+        dom_site = dom_site.split("@")[1] if "@" in dom_site else ""
+
+        # The sampler runs utterance-aligned sub-batches on concurrent streams (kernel switch sampler_streams, read back
+        # from the library), so a launch's HIP-event duration includes time shared with the other streams' kernels. One
+        # extra untimed step with the sampler on a single stream gives the dominant call site's isolated per-launch rate.
+        streams = int(eng.get_config("tune.sampler_streams"))
+        if streams > 1 and dom_site.startswith("diffsvc.") and not args.no_isolated_pass:
+            eng.tune(sampler_streams=1)
+            _lib.profile_enable(True)
+            step()
+            torch.cuda.synchronize()
+            iso = _lib.profile_read()
+            _lib.profile_enable(False)
+            eng.tune(sampler_streams=streams)
+            at_site = {n.split("@")[0]: v for n, v in iso.items() if n.endswith("@" + dom_site)}
+            if at_site:
+                k, v = max(at_site.items(), key=lambda kv: kv[1]["ms"])
+                us = v["ms"] * 1000.0 / v["launches"]
+                tf = v["flops"] / v["launches"] / (us * 1e-6) / 1e12
+                isolated = {"kernel": k, "site": dom_site, "avg_launch_us": round(us, 2), "achieved": round(tf, 2),
+                            "frac": round(tf / PEAK_F16_TFLOPS, 4), "sampler_streams": 1, "launches": v["launches"]}
 
     # The timed steps run with no HIP events at all: one extra untimed production step after them (same configuration,
     # every launch of the dominant kernel between its own event pair) gives the roofline's per-launch figures. Event
     # pairs around the ~2 000 gate launches per step cost 2 % of the step (r04m: 866.4 / 867.6 with them against
     # 884.4 / 883.4 audio-s/s without, alternating); BENCH_TIMED_EVENTS=1 puts them back into the timed region.
-    timed_events = os.environ.get("BENCH_TIMED_EVENTS", "0") == "1"
+    # A plain run has none of this: no events, no clock sampling thread, no step beyond the warmup and timed ones.
+    timed_events = args.full and os.environ.get("BENCH_TIMED_EVENTS", "0") == "1"
     dist.barrier()
     torch.cuda.synchronize()
     if timed_events:
         _lib.profile_filter(dom_name)
         _lib.profile_enable(True)
     gather_s.clear()
-    clocks = ClockSampler(dist.local_rank)
-    clocks.start()
+    clocks = ClockSampler(dist.local_rank) if args.full else None
+    if clocks:
+        clocks.start()
     t0 = time.time()
     for i in range(args.steps):
-        out = step()
+        out, res = step()
         torch.cuda.synchronize()
         log(f"step {i + 1}/{args.steps} {time.time() - t0:.2f}s")
     torch.cuda.synchronize()
     dist.barrier()
     per_rank = [r[0] for r in dist.all_gather_floats([time.time() - t0])]
-    clocks.stop()
+    if clocks:
+        clocks.stop()
     gather_ms = [r[0] for r in dist.all_gather_floats([1000.0 * sum(gather_s) / max(len(gather_s), 1)])]
     elapsed = max(per_rank)
+    ms_per_step = 1000.0 * elapsed / args.steps
+    audio_s = dist.world * B * args.seconds
+    value = audio_s / (elapsed / args.steps)
+    if out is not None:
+        assert out.shape[0] == dist.world * B and bool(torch.isfinite(out).all())
+    # the last timed step's outputs, copied out before any later step reuses the engine's buffers
+    if args.dump_outputs and dist.rank == 0:
+        dump_outputs(args.dump_outputs, {"wav": out.cpu().numpy(), "mel": res.mel.cpu().numpy(),
+                                         "f0": res.f0.cpu().numpy(), "x0": res.x0.cpu().numpy()})
+    T_frames = int((d24.shape[1] + 768 - 1024) // 256 + 1)
+    line = {
+        "metric": "converted audio sec/sec (RTF^-1) end-to-end, 10 s clips",
+        "value": round(value, 2), "unit": "audio-s/s", "n_gpus": dist.world, "steps": args.steps,
+        "dist_world": dist.world, "backend": dist.backend or "none",
+        # the process group's own size (torch.distributed.get_world_size(); 1 without a group) and the gather's
+        # wall time per step on each rank (rank 0 receives; world 1: no collective)
+        "rccl_world": torchdist.get_world_size() if torchdist.is_initialized() else 1,
+        "gather_ms_per_step": [round(v, 3) for v in gather_ms],
+        "per_rank_ms_per_step": [round(1000.0 * t / args.steps, 2) for t in per_rank],
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.operands, "data": "synthetic",
+        "config": {"workload": f"batch={B}/GPU x {args.seconds:g} s synthetic clips, "
+                               + ("Whisper-medium" if hs is None else "HuBERT/ContentVec (layer 9)")
+                               + (f" + PLMS-100 DiffSVC (speedup {args.speedup})" if fast else " + DDPM-1000 DiffSVC")
+                               + f" + BigVGAN, {args.operands} MFMA operands (BigVGAN fp16) / fp32 accumulate"
+                               + {"split": ", split-fp16 content encoder + DiffSVC head (mel-L1 <= 1e-3 mode)",
+                                  "wsplit": ", weight-split Whisper attention linears (all blocks) + MLP linears "
+                                            "(blocks 0-3) + split-fp16 stem / DiffSVC head",
+                                  "fp16": ", plain fp16 operands (mel-L1 target not met)"}[args.precision],
+                   "global_batch": dist.world * B, "seq_len_frames": T_frames,
+                   "parallelism": f"dp{dist.world} (per-utterance shards, RCCL gather)"},
+        "full": args.full,
+    }
+    if not args.full:
+        if dist.rank == 0:
+            print(json.dumps(line), flush=True)
+        dist.close()
+        return
+
     if not timed_events:
         _lib.profile_filter(dom_name)
         _lib.profile_enable(True)
@@ -529,11 +610,6 @@ def main():
     prof = _lib.profile_read()
     _lib.profile_enable(False)
     _lib.profile_filter("")
-    ms_per_step = 1000.0 * elapsed / args.steps
-    audio_s = dist.world * B * args.seconds
-    value = audio_s / (elapsed / args.steps)
-    if out is not None:
-        assert out.shape[0] == dist.world * B and bool(torch.isfinite(out).all())
 
     # Roofline of the dominant kernel AS THE TIMED REGION RUNS IT (its production launches: at a diffsvc.* site the
     # sampler's utterance-aligned sub-batches on `streams` concurrent streams), HIP events around each launch on its
@@ -561,7 +637,6 @@ def main():
                                            dom["bytes"] / dom["launches"], 1)
     roof["share_of_kernel_time"] = round(share, 3)
     roof["sampler_streams"] = streams
-    T_frames = int((d24.shape[1] + 768 - 1024) // 256 + 1)
     if dom_site.startswith("diffsvc."):
         roof["rows_per_launch"] = -(-B // streams) * T_frames  # the largest sub-batch
     roof["measured"] = ("production launches in the timed region, HIP events on the launch stream" if timed_events else
@@ -629,27 +704,7 @@ def main():
         cpu = cpu_baseline(cfg, ws, ms, vs, args.seconds, args.speedup, args.cpu_threads or threads, hs=hs,
                            fast=fast, host=host)
     if dist.rank == 0:
-        line = {
-            "metric": "converted audio sec/sec (RTF^-1) end-to-end, 10 s clips",
-            "value": round(value, 2), "unit": "audio-s/s", "n_gpus": dist.world, "steps": args.steps,
-            "dist_world": dist.world, "backend": dist.backend or "none",
-            # the process group's own size (torch.distributed.get_world_size(); 1 without a group) and the gather's
-            # wall time per step on each rank (rank 0 receives; world 1: no collective)
-            "rccl_world": torchdist.get_world_size() if torchdist.is_initialized() else 1,
-            "gather_ms_per_step": [round(v, 3) for v in gather_ms],
-            "per_rank_ms_per_step": [round(1000.0 * t / args.steps, 2) for t in per_rank],
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.operands, "data": "synthetic",
-            "config": {"workload": f"batch={B}/GPU x {args.seconds:g} s synthetic clips, "
-                                   + ("Whisper-medium" if hs is None else "HuBERT/ContentVec (layer 9)")
-                                   + (f" + PLMS-100 DiffSVC (speedup {args.speedup})" if fast else " + DDPM-1000 DiffSVC")
-                                   + f" + BigVGAN, {args.operands} MFMA operands (BigVGAN fp16) / fp32 accumulate"
-                                   + {"split": ", split-fp16 content encoder + DiffSVC head (mel-L1 <= 1e-3 mode)",
-                                      "wsplit": ", weight-split Whisper attention linears (all blocks) + MLP linears "
-                                                "(blocks 0-3) + split-fp16 stem / DiffSVC head",
-                                      "fp16": ", plain fp16 operands (mel-L1 target not met)"}[args.precision],
-                       "global_batch": dist.world * B, "seq_len_frames": int((d24.shape[1] + 768 - 1024) // 256 + 1),
-                       "parallelism": f"dp{dist.world} (per-utterance shards, RCCL gather)"},
+        line.update({
             "roofline": roof, "cpu_baseline": cpu,
             # box speed beside the value: rank 0's GPU clocks sampled through the timed region, and a fixed hipBLASLt
             # GEMM / HBM copy calibration timed in this process after it (calib_us = that GEMM's time per launch)
@@ -664,7 +719,7 @@ def main():
             "kernels_profiled_step": "last warmup step, every launch bracketed by HIP events (sampler sub-batches on "
                                      f"{streams} concurrent streams: their per-launch times overlap)",
             "kernels": kernels,
-        }
+        })
         print(json.dumps(line), flush=True)
     dist.close()
 

@@ -13,7 +13,7 @@ fi
 for r in $(seq 1 ${ROUNDS:-2}); do
   for cfg in ${SETTINGS:--}; do
     envs=""; [ "$cfg" != "-" ] && envs=$(echo "$cfg" | tr ',' ' ')
-    env $envs timeout -k 10 300 python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 > $O/b.json 2> $O/b.err || { tail -5 $O/b.err; exit 1; }
+    env $envs timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $O/b.json 2> $O/b.err || { tail -5 $O/b.err; exit 1; }
     cp $O/b.json "$O/b_${r}_$(echo "$cfg" | tr '=,/' '__-').json"
     python3 - $O/b.json "$cfg" "${KPAT:-.}" <<'PY'
 import json, re, sys

@@ -22,7 +22,7 @@ for L in $LIBS; do
 done
 for r in $(seq 1 ${ROUNDS:-2}); do
   for L in $LIBS; do
-    SVC_HIP_LIB=$PWD/$L timeout -k 10 300 python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 > $O/b.json 2> $O/b.err || exit $?
+    SVC_HIP_LIB=$PWD/$L timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $O/b.json 2> $O/b.err || exit $?
     python3 - $O/b.json $(basename $L) <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ rc=$?; tail -2 $O/tests.log; [ $rc -ne 0 ] && { grep -E "Error|assert|FAIL" $O/t
 TAG=${TAG:-ab_sampler} ROUNDS=${ROUNDS:-3} bash tools/ab_lib.sh || exit $?
 if [ -n "${TRACE:-}" ]; then
   export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace -f csv -d $O/trace -o run -- python3 bench.py --steps 2 --warmup 1 \
+  timeout -k 10 600 rocprofv3 --kernel-trace -f csv -d $O/trace -o run -- python3 bench.py --full --steps 2 --warmup 1 \
     --no-cpu-baseline > $O/trace_bench.json 2> $O/trace_bench.err || exit $?
   python3 tools/stream_gaps.py $O/trace
 fi

@@ -16,9 +16,9 @@ HB=$!
 trap "kill $HB 2>/dev/null" EXIT
 STEPS=${STEPS:-3}
 if [ -z "${PMC_ONLY:-}" ]; then
-timeout -k 10 900 python3 bench.py --steps $STEPS --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 900 python3 bench.py --full --steps $STEPS --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
 echo "bench done"; tail -c 600 $OUT/bench.json
-timeout -k 10 900 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/trace_bench.json 2> $OUT/trace_bench.err
+timeout -k 10 900 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/trace_bench.json 2> $OUT/trace_bench.err
 echo "trace done"
 fi
 # rocprofv3 matches the kernel symbol as recorded (templates with bool parameters stay mangled): derive the
@@ -39,8 +39,8 @@ PY
 )
 fi
 echo "PMC kernel regex: $KRE"
-timeout -k 10 900 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRE" -f csv -d $OUT/pmc_fetch -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $OUT/pmc_fetch.err
+timeout -k 10 900 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex "$KRE" -f csv -d $OUT/pmc_fetch -o run -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $OUT/pmc_fetch.err
 echo "pmc fetch done"
-timeout -k 10 900 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$KRE" -f csv -d $OUT/pmc_write -o run -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $OUT/pmc_write.err
+timeout -k 10 900 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "$KRE" -f csv -d $OUT/pmc_write -o run -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > /dev/null 2> $OUT/pmc_write.err
 echo "pmc write done"
 find $OUT -name "*.csv" | head -20

@@ -18,7 +18,7 @@ for set in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU
   i=$((i+1))
   case " ${PASSES:-1 2 3 4} " in *" $i "*) ;; *) continue ;; esac
   timeout -k 10 ${PASS_TIMEOUT:-300} rocprofv3 --pmc $set --kernel-include-regex "$KRE" -f csv -d $O/p$i -o run -- \
-    python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline > $O/p$i.log 2>&1 || { rc=$?; echo "pass $i failed (exit $rc)"; tail -5 $O/p$i.log; exit 1; }
+    python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $O/p$i.log 2>&1 || { rc=$?; echo "pass $i failed (exit $rc)"; tail -5 $O/p$i.log; exit 1; }
   echo "pass $i done"
 done
 [ -n "${NOSUM:-}" ] && exit 0  # passes split over calls: summarised where all of them are

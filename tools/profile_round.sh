@@ -16,6 +16,6 @@ for c in $SET; do grep -q "\b$c\b" gpurun_out/$TAG/counters.txt || { echo "count
 if [ $ok = 1 ]; then
   O=gpurun_out/${TAG}_issue; mkdir -p $O
   timeout -k 10 300 rocprofv3 --pmc $SET --kernel-include-regex "gate_ws_kernel" -f csv -d $O/p5 -o run -- \
-    python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline > $O/p5.log 2>&1 && echo "issue pass done"
+    python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline > $O/p5.log 2>&1 && echo "issue pass done"
   python3 tools/pmc_kernels.py $O $O/summary.json > $O/summary.txt; cat $O/summary.txt
 fi
