@@ -188,11 +188,27 @@ svc_status svc_resample(const float* x, int B, int64_t n_in, int sr_in, int sr_o
 svc_status svc_resample_filter(int sr_in, int sr_out, double* h, int cap, int* n, int* up, int* down,
                                int* pre_remove);
 /* BigVGAN AMP step for small channel counts: y = conv_k,d(Activation1d(x)) + bias (+ add_row), fused.
- * x, add_row, y f32 [B*L][C] time-major; w f32 [C][C][k] (effective weight); C in {24, 48, 96}.
+ * x, add_row, y f32 [B*L][C] time-major; w f32 [C][C][k] (effective weight); C in {24, 48, 96, 192}.
  * Replaces modules/bigvgan.py:427-431 (a1/c1, a2/c2 pairs) for the late generator stages. */
 svc_status svc_op_amp_conv(const float* x, int B, int L, int C, const float* alpha_log, const float* beta_log,
                            const float* filt, const float* w, const float* bias, int k, int d, const float* add_row,
                            float* y, void* stream);
+/* The same kernel with every operand svc_bigvgan gives it (the parity tests): input x (f32) or x16 (binary16), exactly
+ * one of them; ragged lengths tv [B] (utterance b has min(L, tv[b] * tv_mul) rows, rows past that are left untouched;
+ * NULL = all L); epilogue v = conv + bias (+ add_row), then v = (acc32 + v) / acc_div when acc32 is given; outputs out32
+ * (f32, may be acc32 or add_row itself) and / or out16 (binary16, saturating). All tensors [B*L][C]; C in
+ * {24, 48, 96, 192}. svc_op_amp_conv is this with x, add_row and out32 only. */
+svc_status svc_op_amp_conv_ex(const float* x, const void* x16, int B, int L, int C, const float* alpha_log,
+                              const float* beta_log, const float* filt, const float* w, const float* bias, int k, int d,
+                              const int32_t* tv, int tv_mul, const float* add_row, const float* acc32, float acc_div,
+                              float* out32, void* out16, void* stream);
+/* The rate-2 ConvTranspose1d of BigVGAN's late stages as svc_bigvgan runs it (tune.amp_ups): one plain conv over the
+ * input rows with the combined packing of both output phases. x16 binary16 [B*T_in][Cin], w f32 [Cin][Cout][k] (no
+ * weight norm), pad = (k - stride) / 2, tv / tv_mul as above, y f32 [B*stride*T_in][Cout]. SVC_ERR_INVALID for a shape
+ * without a combined form (anything but stride 2, k 4, Cin = 2 Cout in {48, 96, 192}): nothing else is run. */
+svc_status svc_op_conv_transpose1d_comb(const void* x16, int B, int T_in, int Cin, const float* w, const float* bias,
+                                        int Cout, int k, int stride, const int32_t* tv, int tv_mul, float* y,
+                                        void* stream);
 /* Activation1d(SnakeBeta, logscale): x f32 [B*L][C] -> y f32 [B*L][C] */
 svc_status svc_op_activation1d(const float* x, int B, int L, int C, const float* alpha_log, const float* beta_log,
                                const float* filt12, float* y, void* stream);

@@ -396,7 +396,8 @@ static int launch_amp(const AmpConvArgs& p, const EpiArgs& e, hipStream_t s) {
   const double bytes =
       elems * ((X16 ? 2.0 : 4.0) + (e.out32 ? 4 : 0) + (e.out16 ? 2 : 0) + (e.add_row ? 4 : 0) + (e.acc32 ? 4 : 0));
   const char* tag = NOACT ? (C == 48 ? "amp_conv<48,conv>" : (C == 96 ? "amp_conv<96,conv>" : "amp_conv<192,conv>"))
-                          : (C == 24 ? "amp_conv<24>" : (C == 48 ? "amp_conv<48>" : (C == 96 ? "amp_conv<96>" : "amp_conv<192>")));
+                   : X16 ? (C == 24 ? "amp_conv<24,x16>" : (C == 48 ? "amp_conv<48,x16>" : (C == 96 ? "amp_conv<96,x16>" : "amp_conv<192,x16>")))
+                         : (C == 24 ? "amp_conv<24>" : (C == 48 ? "amp_conv<48>" : (C == 96 ? "amp_conv<96>" : "amp_conv<192>")));
   const int tok = prof_begin(tag, 2.0 * elems * C * p.k, bytes, s);
   // the activation image needs BT + 2P rows, not BT + 2 MAXP: sized per launch, C = 48 fits 5 workgroups per CU
   // (instead of 4) for every conv with P <= 15

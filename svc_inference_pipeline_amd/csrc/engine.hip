@@ -2887,28 +2887,83 @@ svc_status svc_op_conv1d(const float* x, int B, int T_in, int Cin, const float* 
   return st;
 }
 
-svc_status svc_op_amp_conv(const float* x, int B, int L, int C, const float* alpha_log, const float* beta_log,
-                           const float* filt, const float* w, const float* bias, int k, int d, const float* add_row,
-                           float* y, void* stream) {
+svc_status svc_op_amp_conv_ex(const float* x, const void* x16, int B, int L, int C, const float* alpha_log,
+                              const float* beta_log, const float* filt, const float* w, const float* bias, int k, int d,
+                              const int32_t* tv, int tv_mul, const float* add_row, const float* acc32, float acc_div,
+                              float* out32, void* out16, void* stream) {
   svc_ctx* c;
   op_ws(&c);
   TuningScope tuning_scope_(&c->tune);
   hipStream_t s = (hipStream_t)stream;
-  SVC_REQUIRE(amp_conv_supported(C, k, d), "op_amp_conv: C=%d k=%d d=%d unsupported", C, k, d);
+  SVC_REQUIRE(amp_conv_supported(C, k, d) && d > 0, "op_amp_conv: C=%d k=%d d=%d unsupported", C, k, d);
+  SVC_REQUIRE((x != nullptr) != (x16 != nullptr), "op_amp_conv: exactly one of x (f32) and x16 (f16)");
+  SVC_REQUIRE(out32 || out16, "op_amp_conv: no output");
   std::vector<float> wh, bh;
   PackedGemm g;
   int st;
   if ((st = pack_from_device(c, g, w, (size_t)C * C * k, bias, C, wh, bh))) return st;
   if ((st = pack_conv1d(c, g, wh.data(), bh.data(), C, C, k, C, d, (k - 1) / 2 * d, 1))) return st;
+  // the epilogue fields as svc_bigvgan sets them (c1: out16 only; c2: add_row + out32; resblock sum / mean: + acc32
+  // (+ acc_div), out32 possibly acc32 itself)
   EpiArgs e = epi();
-  e.out32 = y;
+  e.out32 = out32;
   e.ld32 = C;
+  e.out16 = (f16*)out16;
+  e.ld16 = C;
   e.add_row = add_row;
   e.ld_add_row = C;
-  const AmpConvArgs p{x, B, L, k, d, alpha_log, beta_log, filt, g.W, g.Kpad, g.bias};
+  e.acc32 = acc32;
+  e.ld_acc = C;
+  if (acc32) e.acc_div = acc_div;
+  AmpConvArgs p{x, B, L, k, d, alpha_log, beta_log, filt, g.W, g.Kpad, g.bias};
+  p.x16 = (const f16*)x16;
+  p.tv = tv;
+  p.tv_mul = tv_mul;
   st = amp_conv(p, C, e, s);
   (void)hipStreamSynchronize(s);
   free_packed(c, g);
+  return st;
+}
+
+svc_status svc_op_amp_conv(const float* x, int B, int L, int C, const float* alpha_log, const float* beta_log,
+                           const float* filt, const float* w, const float* bias, int k, int d, const float* add_row,
+                           float* y, void* stream) {
+  return svc_op_amp_conv_ex(x, nullptr, B, L, C, alpha_log, beta_log, filt, w, bias, k, d, nullptr, 1, add_row, nullptr,
+                            1.0f, y, nullptr, stream);
+}
+
+svc_status svc_op_conv_transpose1d_comb(const void* x16, int B, int T_in, int Cin, const float* w, const float* bias,
+                                        int Cout, int k, int stride, const int32_t* tv, int tv_mul, float* y,
+                                        void* stream) {
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  SVC_REQUIRE(x16 && y && B > 0 && T_in > 0 && Cin > 0 && Cout > 0 && k > 0 && stride > 0, "op_conv_transpose1d_comb: bad args");
+  std::vector<float> wh, bh;
+  int st;
+  VStage S;
+  S.cin = Cin;
+  S.cout = Cout;
+  S.rate = stride;
+  S.k = k;
+  if ((st = pack_from_device(c, S.upc, w, (size_t)Cout * Cin * k, bias, Cout, wh, bh))) return st;
+  if ((st = pack_conv_transpose_comb(c, S, wh.data(), nullptr, bh.data()))) return st;
+  // no other path: a shape the packer declines is an error here (svc_bigvgan runs the phase GEMMs for it)
+  SVC_REQUIRE(S.up_comb, "op_conv_transpose1d_comb: cin=%d cout=%d k=%d stride=%d has no combined form", Cin, Cout, k,
+              stride);
+  // as svc_bigvgan's up-sampling: k = 3, d = -1, the f16 stage input, out32 rows [B*T_in][2 cout] = [B*2 T_in][cout]
+  AmpConvArgs q{nullptr, B, T_in, 3, -1, nullptr, nullptr, nullptr, S.upc.W, S.upc.Kpad, S.upc.bias};
+  q.x16 = (const f16*)x16;
+  q.noact = true;
+  q.tv = tv;
+  q.tv_mul = tv_mul;
+  EpiArgs u = epi();
+  u.out32 = y;
+  u.ld32 = S.cin;
+  st = amp_conv(q, S.cin, u, s);
+  (void)hipStreamSynchronize(s);
+  free_packed(c, S.upc);
   return st;
 }
 

@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import amp_ref as AR  # noqa: E402
 from gpu_util import call, dev, ptr, rel_l2, stream  # noqa: E402
 from oracle import models as OM  # noqa: E402
 
@@ -131,6 +132,150 @@ def test_amp_conv(B, L, k, d, C):
          stream())
     out = y.cpu().view(B, L, C).permute(0, 2, 1).numpy()
     assert rel_l2(out, ref.numpy()) < 2e-3
+
+
+class _Gpu:
+    """amp_ref backend: the library's op-level entry points (svc_op_amp_conv_ex, svc_op_conv_transpose1d_comb, the
+    amp_conv calls svc_bigvgan makes)."""
+
+    def amp_conv(self, x, x16, al, be, f, w, bias, k, d, tv, tv_mul, add_row, acc32, acc_div, out32, out16):
+        B, L, C = x.shape
+        xd = dev(x, torch.float16 if x16 else torch.float32)
+        ad, bd, fd, wd, bbd = dev(al), dev(be), dev(f), dev(w), dev(bias)
+        tvd = None if tv is None else dev(np.asarray(tv, np.int32), torch.int32)
+        rd = None if add_row is None else dev(add_row)
+        cd = None if acc32 is None else dev(acc32)
+        o32 = cd if isinstance(out32, str) else (None if out32 is None else dev(out32))
+        o16 = None if out16 is None else dev(out16, torch.float16)
+        call("svc_op_amp_conv_ex", None if x16 else ptr(xd), ptr(xd) if x16 else None, B, L, C, ptr(ad), ptr(bd),
+             ptr(fd), ptr(wd), ptr(bbd), k, d, ptr(tvd), tv_mul, ptr(rd), ptr(cd), float(acc_div), ptr(o32), ptr(o16),
+             stream())
+        return (None if o32 is None else o32.cpu().numpy()), (None if o16 is None else o16.cpu().numpy())
+
+    def ups_comb(self, x, w, bias, k, s, tv, tv_mul, out):
+        B, T, cin = x.shape
+        xd, wd, bd, od = dev(x, torch.float16), dev(w), dev(bias), dev(out)
+        tvd = None if tv is None else dev(np.asarray(tv, np.int32), torch.int32)
+        call("svc_op_conv_transpose1d_comb", ptr(xd), B, T, cin, ptr(wd), ptr(bd), w.shape[1], k, s, ptr(tvd), tv_mul,
+             ptr(od), stream())
+        return od.cpu().numpy()
+
+    def ups_phase(self, x, w, bias, k, s):
+        B, T, cin = x.shape
+        xd, wd, bd = dev(x), dev(w), dev(bias)
+        y = torch.empty(B, T * s, w.shape[1], device="cuda")
+        call("svc_op_conv_transpose1d", ptr(xd), B, T, cin, ptr(wd), ptr(bd), w.shape[1], k, s, (k - s) // 2, ptr(y),
+             stream())
+        return y.cpu().numpy()
+
+
+class _Launched:
+    """The amp_conv kernel forms launched inside the block, by profiler tag ("amp_conv<C>", "<C,x16>", "<C,conv>")."""
+
+    def __enter__(self):
+        from svc_inference_pipeline_amd import _lib
+        _lib.profile_enable(True)
+        self.tags = None
+        return self
+
+    def __exit__(self, *exc):
+        from svc_inference_pipeline_amd import _lib
+        try:
+            if exc[0] is None:
+                ran = _lib.profile_read()
+                self.tags = {n.split("@")[0] for n, v in ran.items() if n.startswith("amp_conv") and v["launches"] > 0}
+        finally:
+            _lib.profile_enable(False)
+
+
+_AMP_CASES = {C: {c[0]: c[1:] for c in AR.length_cases(C)} for C in (24, 48, 96, 192)}
+_AMP_LEN_NAMES = ["Lm1", "L0", "Lp1", "L2p1", "ragged", "ragged_mul8", "L1", "L2", "L5", "L13"]
+
+
+def _amp_case(C, name):
+    BT = AR.tile_rows(C)
+    key = {"Lm1": "L%d" % (BT - 1), "L0": "L%d" % BT, "Lp1": "L%d" % (BT + 1), "L2p1": "L%d" % (2 * BT + 1)}.get(name, name)
+    return _AMP_CASES[C][key]
+
+
+@pytest.mark.parametrize("length", _AMP_LEN_NAMES)
+@pytest.mark.parametrize("x16", [False, True])
+@pytest.mark.parametrize("C", [24, 48, 96, 192])
+def test_amp_conv_tap_probes(C, x16, length):
+    """The activation image amp_conv builds in LDS, element by element (amp_ref.check_tap_probes): one-tap identity
+    weights make out32 the f16 image row each tap reads, halo rows and zero padding included. Lengths (BT = 512 rows for
+    C <= 48, 256 otherwise): BT - 1, BT, BT + 1, 2 BT + 1; a ragged batch ending on, one past and far before a tile edge,
+    and with a clamping frame multiplier; 1, 2, 5, 13 rows. (k, d) = (11, 5), (3, 1), (7, 5), first / centre / last tap;
+    every utterance also bit-equal to itself run alone.
+    Largest observed on MI355X: rel-L2 1.2e-5, element ratio |d| / (|ref| + 1e-2) 9.8e-4 (bounds 1e-3, 5e-3): the image
+    differs from the f64 reference's f16 rounding by single f16 ulps only."""
+    B, L, tv, mul = _amp_case(C, length)
+    with _Launched() as ran:
+        l2, el = AR.check_tap_probes(_Gpu(), C, x16, B, L, tv, mul, [(11, 5), (3, 1), (7, 5)])
+    print("amp_conv tap probes C=%d x16=%d %s: rel-L2 %.3e element %.3e" % (C, x16, length, l2, el))
+    assert ran.tags == {"amp_conv<%d%s>" % (C, ",x16" if x16 else "")}, ran.tags
+
+
+@pytest.mark.parametrize("length", _AMP_LEN_NAMES)
+@pytest.mark.parametrize("k,d", [(11, 5), (7, 3), (3, 1)])
+@pytest.mark.parametrize("C", [24, 48, 96, 192])
+def test_amp_conv_epilogues(C, k, d, length):
+    """Conv + each epilogue svc_bigvgan uses (c1: out16 only; c2: add_row + out32; the resblock sum in place:
+    + acc32 with out32 = acc32; the resblock mean: + acc_div = 3 to out16, and to out32 in place) against the f64 sum
+    of the kernel's own A operands (its k tap probes) times the f16-rounded weights, every element within
+    2 K 2^-24 S + 2^-23 |ref| (+ 2^-11 |ref| for f16), K = k C; rows past each utterance's end bit-untouched.
+    f16 input at C = 24 / 96, f32 at 48 / 192.
+    Largest observed err / bound on MI355X: f32 outputs 0.015 (C = 24), 0.0072 (48), 0.0036 (96), 0.0017 (192); f16
+    outputs 0.95 / 0.88 / 0.80 / 0.64: an f16 output's bound is mostly its own half ulp, which a rounding reaches."""
+    x16 = C in (24, 96)
+    B, L, tv, mul = _amp_case(C, length)
+    with _Launched() as ran:
+        w32, w16 = AR.check_epilogues(_Gpu(), C, x16, B, L, tv, mul, k, d)
+    print("amp_conv epilogues C=%d k=%d d=%d %s: err/bound f32 %.4f f16 %.4f" % (C, k, d, length, w32, w16))
+    assert ran.tags == {"amp_conv<%d%s>" % (C, ",x16" if x16 else "")}, ran.tags
+
+
+@pytest.mark.parametrize("C,x16", [(24, False), (96, True)])
+def test_amp_conv_f16_saturation(C, x16):
+    """A bias of 1e5 in two channels: out16 reads 65504 there (f16_sat), finite everywhere, on the ragged batch."""
+    B, L, tv, mul = _amp_case(C, "ragged")
+    AR.check_saturation(_Gpu(), C, x16, B, L, tv, mul, 3, 1)
+
+
+_UPS_NAMES = ["T1", "T2", "T40", "Tm1", "T0", "Tp1", "ragged", "ragged_mul4"]
+
+
+@pytest.mark.parametrize("length", _UPS_NAMES)
+@pytest.mark.parametrize("cin", [48, 96, 192])
+def test_conv_transpose1d_comb(cin, length):
+    """The rate-2 ConvTranspose1d as svc_bigvgan's combined conv (pack_conv_transpose_comb + amp_conv's plain-conv form,
+    k = 3, d = -1) against an f64 conv_transpose1d of the f16-rounded input and weights, every element within the
+    accumulation bound (K = 2 cin); rows >= 2 Lb untouched; at cin 96 / 192 bit-identical to the phase GEMMs
+    (svc_op_conv_transpose1d) on the same input, at cin 48 within the bound only (the 32-deep MFMA steps straddle taps).
+    T = 1, 2, 40, BT - 1, BT, BT + 1 and ragged batches.
+    Largest observed err / bound on MI355X: 0.0080 at cin 48, 0.0042 at 96, 0.0024 at 192."""
+    BT = AR.tile_rows(cin)
+    key = {"Tm1": "T%d" % (BT - 1), "T0": "T%d" % BT, "Tp1": "T%d" % (BT + 1)}.get(length, length)
+    B, T, tv, mul = {c[0]: c[1:] for c in AR.ups_cases(cin)}[key]
+    with _Launched() as ran:
+        worst = AR.check_ups(_Gpu(), cin, B, T, tv, mul)
+    print("conv_transpose1d_comb cin=%d %s: err/bound %.4f" % (cin, length, worst))
+    assert ran.tags == {"amp_conv<%d,conv>" % cin}, ran.tags
+
+
+@pytest.mark.parametrize("cin,cout,k,s", [(384, 192, 4, 2), (96, 24, 4, 2), (96, 48, 8, 4)])
+def test_conv_transpose1d_comb_rejects(cin, cout, k, s):
+    """Shapes without a combined form are an error (SVC_ERR_INVALID), not another path: nothing is launched or written."""
+    from svc_inference_pipeline_amd import _lib
+    T = 9
+    xd, wd, bd = dev(np.ones((T, cin)), torch.float16), dev(np.ones((cin, cout, k))), dev(np.zeros(cout))
+    y = torch.full((T * s, cout), float(AR.SENT32), device="cuda")
+    with _Launched() as ran:
+        with pytest.raises(_lib.SVCError, match="status 1:.*no combined form"):
+            call("svc_op_conv_transpose1d_comb", ptr(xd), 1, T, cin, ptr(wd), ptr(bd), cout, k, s, None, 1, ptr(y),
+                 stream())
+    assert ran.tags == set()
+    assert bool((y == float(AR.SENT32)).all())
 
 
 def test_bigvgan_activation_launch_chunks():

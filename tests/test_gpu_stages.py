@@ -362,10 +362,22 @@ def test_bigvgan_ups_combined(engine, tune):
     rounding (rel-L2 < 1e-5), not bit for bit."""
     rng = np.random.default_rng(11)
     x = dev(rng.uniform(-1, 1, (3, 41, 100)).astype(np.float32))
-    outs = {}
+    outs, ran = {}, {}
     for v in ("0", "1"):
         tune(engine, amp_ups=v)
-        outs[v] = (engine.bigvgan(x).cpu().numpy(), engine.bigvgan(x, frames=[41, 23, 33]).cpu().numpy())
+        _lib.profile_enable(True)
+        try:
+            outs[v] = (engine.bigvgan(x).cpu().numpy(), engine.bigvgan(x, frames=[41, 23, 33]).cpu().numpy())
+            ran[v] = _lib.profile_read()
+        finally:
+            _lib.profile_enable(False)
+    # the combined kernel ran for every rate-2 stage it covers, and only when switched on (no case passes by running
+    # the phase GEMMs on both sides)
+    comb = {v: {n.split("@")[0]: r["launches"] for n, r in ran[v].items() if n.startswith("amp_conv<") and ",conv>" in n}
+            for v in ran}
+    assert comb["0"] == {}, comb["0"]
+    assert set(comb["1"]) == {"amp_conv<48,conv>", "amp_conv<96,conv>", "amp_conv<192,conv>"}, comb["1"]
+    assert all(n > 0 for n in comb["1"].values())
     for i in range(2):
         a, b = outs["0"][i], outs["1"][i]
         assert rel_l2(b, a) < 1e-5, (i, rel_l2(b, a))
