@@ -219,6 +219,26 @@ svc_status svc_op_activation1d_x16(const void* x16, int B, int L, int C, const f
 svc_status svc_op_attention(const float* q, const float* k, const float* v, int B, int L, int D, float* out,
                             void* stream);
 svc_status svc_op_layernorm(const float* x, const float* g, const float* b, int rows, int D, float* y, void* stream);
+/* The sampler's element-wise kernels exactly as svc_diffsvc_sample launches them (the parity tests; no copies, every
+ * pointer a device pointer). x16 is the 16-bit copy for the next GEMM, rows of ld16 >= C halves of which columns
+ * 0..C-1 are written: binary16, or bfloat16 bits with bf16 = 1.
+ * svc_op_init_noise: x [B*T][C] = std * N(0, 1), the x_T draw: Philox4x32-10 with counter {t * C + c, 0xFFFFFFFF,
+ * utt_ids[b], 0x5356434B} and key {seed low word, seed high word}, Box-Muller on its first two words. x16 is required. */
+svc_status svc_op_init_noise(uint64_t seed, const int32_t* utt_ids, int B, int T, int C, float std, float* x, void* x16,
+                             int ld16, int bf16, void* stream);
+/* One PLMS update on [rows][C]: e' = (c0 e0 + c1 e1 + ...) / div over the first ne (1..4) histories (the others may
+ * be NULL), xout = xin + d (A xin - Bc e'); xout may be xin. Optional outputs: x16 and e_avg_out (e'). Four channels
+ * per thread when C % 4 == 0, ld16 % 4 == 0, the f32 pointers are 16-byte and x16 8-byte aligned, else one. */
+svc_status svc_op_plms_update(const float* e0, const float* e1, const float* e2, const float* e3, float c0, float c1,
+                              float c2, float c3, int ne, float div, float d, float A, float Bc, const float* xin,
+                              float* xout, void* x16, int ld16, float* e_avg_out, int bf16, int rows, int C,
+                              void* stream);
+/* One DDPM p_sample step in place on x [B*T][C]: x0 = clip(sra x - srm1 eps, -1, 1), x = c1 x0 + c2 x + sigma z.
+ * z [B*T][C] given, or NULL: drawn as in svc_op_init_noise with counter word 1 = step, which needs utt_ids (both NULL
+ * is SVC_ERR_INVALID). x16 is required. */
+svc_status svc_op_ddpm_update(float* x, const float* eps, int B, int T, int C, float sra, float srm1, float c1,
+                              float c2, float sigma, const float* z, uint64_t seed, const int32_t* utt_ids, int step,
+                              void* x16, int ld16, int bf16, void* stream);
 /* live per-kernel timing: enable(1) clears and starts recording (hipEvents around each launch),
    read(idx, ...) synchronises and returns kernel idx's name, total ms, launches, algorithmic FLOPs/bytes;
    n_kernels receives the number of distinct kernels. */

@@ -7,7 +7,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVC_HIP_LIB", os.path.join(_HERE, "libsvc_hip.so"))
 
 c_void_p, c_int, c_int64, c_uint64, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
-c_float_p = ctypes.POINTER(ctypes.c_float)
+c_float = ctypes.c_float
+c_float_p = ctypes.POINTER(c_float)
 
 # name -> (restype, argtypes); every symbol declared in include/svc_hip.h
 PROTOTYPES = {
@@ -58,6 +59,13 @@ PROTOTYPES = {
                                         c_void_p]),
     "svc_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "svc_op_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "svc_op_init_noise": (c_int, [c_uint64, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int,
+                                  c_void_p]),
+    "svc_op_plms_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
+                                   c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_int, c_int, c_int, c_void_p]),
+    "svc_op_ddpm_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                                   c_void_p, c_uint64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "svc_profile_enable": (c_int, [c_int]),
     "svc_profile_filter": (c_int, [ctypes.c_char_p]),
     "svc_profile_read": (c_int, [c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_int64),

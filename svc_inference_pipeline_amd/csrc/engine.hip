@@ -3050,6 +3050,62 @@ svc_status svc_op_layernorm(const float* x, const float* g, const float* b, int 
   return layernorm_f32(x, g, b, y, rows, D, D, (hipStream_t)stream);
 }
 
+// the sampler's element-wise launchers with the arguments sample_impl gives them
+svc_status svc_op_init_noise(uint64_t seed, const int32_t* utt_ids, int B, int T, int C, float std, float* x, void* x16,
+                             int ld16, int bf16, void* stream) {
+  SVC_REQUIRE(utt_ids && x && x16 && B > 0 && T > 0 && C > 0 && ld16 >= C, "op_init_noise: bad args");
+  SVC_REQUIRE((int64_t)B * T * C <= INT32_MAX, "op_init_noise: B*T*C past 2^31");
+  return init_noise(x, (f16*)x16, ld16, B, T, C, seed, utt_ids, std, (hipStream_t)stream, bf16 != 0);
+}
+
+svc_status svc_op_plms_update(const float* e0, const float* e1, const float* e2, const float* e3, float c0, float c1,
+                              float c2, float c3, int ne, float div, float d, float A, float Bc, const float* xin,
+                              float* xout, void* x16, int ld16, float* e_avg_out, int bf16, int rows, int C,
+                              void* stream) {
+  PlmsArgs p{};
+  const float* e[4] = {e0, e1, e2, e3};
+  const float cf[4] = {c0, c1, c2, c3};
+  SVC_REQUIRE(ne >= 1 && ne <= 4 && xin && xout && rows > 0 && C > 0 && (!x16 || ld16 >= C), "op_plms_update: bad args");
+  SVC_REQUIRE((int64_t)rows * C <= INT32_MAX, "op_plms_update: rows*C past 2^31");
+  for (int k = 0; k < ne; ++k) {
+    SVC_REQUIRE(e[k], "op_plms_update: e%d is NULL (ne = %d)", k, ne);
+    p.e[k] = e[k];
+    p.c[k] = cf[k];
+  }
+  p.ne = ne;
+  p.div = div;
+  p.d = d;
+  p.A = A;
+  p.Bc = Bc;
+  p.xin = xin;
+  p.xout = xout;
+  p.x16 = (f16*)x16;
+  p.ld16 = ld16;
+  p.e_avg_out = e_avg_out;
+  p.bf16 = bf16 != 0;
+  return plms_update(p, rows, C, (hipStream_t)stream);
+}
+
+svc_status svc_op_ddpm_update(float* x, const float* eps, int B, int T, int C, float sra, float srm1, float c1,
+                              float c2, float sigma, const float* z, uint64_t seed, const int32_t* utt_ids, int step,
+                              void* x16, int ld16, int bf16, void* stream) {
+  SVC_REQUIRE(x && eps && x16 && B > 0 && T > 0 && C > 0 && ld16 >= C, "op_ddpm_update: bad args");
+  SVC_REQUIRE((int64_t)B * T * C <= INT32_MAX, "op_ddpm_update: B*T*C past 2^31");
+  SVC_REQUIRE(z || utt_ids, "op_ddpm_update: device noise (z NULL) needs utt_ids");
+  DdpmArgs a{};
+  a.sra = sra;
+  a.srm1 = srm1;
+  a.c1 = c1;
+  a.c2 = c2;
+  a.sigma = sigma;
+  a.z = z;
+  a.seed = seed;
+  a.utt_ids = utt_ids;
+  a.step = step;
+  a.bf16 = bf16 != 0;
+  return ddpm_update(x, eps, (f16*)x16, ld16, B, T, C, a, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------- GEMM microbenchmark

@@ -364,3 +364,66 @@ def test_layernorm():
     xd, gd, bd = dev(x), dev(gm), dev(bt)
     call("svc_op_layernorm", ptr(xd), ptr(gd), ptr(bd), 300, 1024, ptr(y), stream())
     np.testing.assert_allclose(y.cpu().numpy(), ref.numpy(), rtol=0, atol=2e-5)
+
+
+def _layernorm_f64(x, g, b):
+    x = x.astype(np.float64)
+    mu = x.mean(axis=1, keepdims=True)
+    var = ((x - mu) ** 2).mean(axis=1, keepdims=True)
+    return (x - mu) / np.sqrt(var + 1e-5) * g.astype(np.float64) + b.astype(np.float64), np.sqrt(var)
+
+
+def _layernorm_run(x, g, b):
+    """svc_op_layernorm into a buffer with 4 guard rows of SENT32 after `rows` -> (y [rows, D], guard rows intact)."""
+    rows, D = x.shape
+    y = torch.full((rows + 4, D), float(AR.SENT32), device="cuda")
+    xd, gd, bd = dev(x), dev(g), dev(b)
+    call("svc_op_layernorm", ptr(xd), ptr(gd), ptr(bd), rows, D, ptr(y), stream())
+    return y[:rows].cpu().numpy(), bool((y[rows:] == float(AR.SENT32)).all())
+
+
+@pytest.mark.parametrize("rows", [1, 3, 5, 301])
+@pytest.mark.parametrize("D", [64, 256, 384, 768, 1024])
+def test_layernorm_forms(D, rows):
+    """Both LayerNorm kernels against float64: layernorm_kernel (D = 64, Whisper-tiny's 384) and layernorm_v4_kernel
+    with nq = 1, 3 (HuBERT's 768) and 4; one row, row counts that leave the last 4-row block partial, and many blocks.
+    N(1, 3^2) data at the project's atol = 2e-5; the rows after `rows` are not written.
+    Largest |y - ref| observed on MI355X: 1.4e-6 (D = 768, 301 rows)."""
+    rng = np.random.default_rng([D, rows])
+    x = (rng.standard_normal((rows, D)) * 3 + 1).astype(np.float32)
+    g, b = rng.standard_normal(D).astype(np.float32), rng.standard_normal(D).astype(np.float32)
+    y, guards = _layernorm_run(x, g, b)
+    ref, _ = _layernorm_f64(x, g, b)
+    print("layernorm D=%d rows=%d: max |d| %.3e" % (D, rows, np.max(np.abs(y - ref))))
+    np.testing.assert_allclose(y, ref, rtol=0, atol=2e-5)
+    assert guards
+
+
+@pytest.mark.parametrize("D", [384, 768])
+def test_layernorm_offset_rows(D):
+    """Rows with a mean far from zero (mean 50, sigma 0.5), one case per kernel form: x - mean cancels two decimal
+    digits, so each output carries the rounding of that difference, <= 4 u max|x| / sigma_row |gamma| (u = 2^-24: the
+    rounding of the f32 mean and of the difference, in units of the row's sigma), on top of the project's 2e-5.
+    Largest err / bound observed on MI355X: 0.28 (D = 384), 0.20 (D = 768)."""
+    rows = 5
+    rng = np.random.default_rng(D)
+    x = (rng.standard_normal((rows, D)) * 0.5 + 50).astype(np.float32)
+    g, b = rng.standard_normal(D).astype(np.float32), rng.standard_normal(D).astype(np.float32)
+    y, guards = _layernorm_run(x, g, b)
+    ref, sig = _layernorm_f64(x, g, b)
+    bound = 2e-5 + 4 * 2.0 ** -24 * np.abs(x).max(axis=1, keepdims=True) / sig * np.abs(g)[None, :]
+    print("layernorm offset D=%d: max err/bound %.3f" % (D, np.max(np.abs(y - ref) / bound)))
+    assert np.all(np.abs(y - ref) <= bound)
+    assert guards
+
+
+@pytest.mark.parametrize("D", [1088, 96])
+def test_layernorm_rejects(D):
+    """A width the kernels have no form for (> 1024, or no multiple of 64) is SVC_ERR_INVALID; nothing is written."""
+    from svc_inference_pipeline_amd import _lib
+    x, g, b = np.ones((3, D), np.float32), np.ones(D, np.float32), np.zeros(D, np.float32)
+    y = torch.full((3, D), float(AR.SENT32), device="cuda")
+    xd, gd, bd = dev(x), dev(g), dev(b)
+    with pytest.raises(_lib.SVCError, match="status 1:.*layernorm: D=%d" % D):
+        call("svc_op_layernorm", ptr(xd), ptr(gd), ptr(bd), 3, D, ptr(y), stream())
+    assert bool((y == float(AR.SENT32)).all())
