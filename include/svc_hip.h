@@ -13,6 +13,8 @@
  *   svc_diffsvc_sample  <- modules/diffsvcrepo_inference.py:154-240 svc_model_inference (DDPM or PLMS)
  *   svc_bigvgan         <- utils/acoustic_feature_extraction.py:83-97 denormalize_mel_channel
  *                          + modules/bigvgan_inference.py:29-44 synthesis_audios (Generator + trim + fade)
+ *   svc_pcm16           <- utils/util.py:20-37 save_audio (peak normalisation, silence, 16-bit samples; the file
+ *                          itself is written on the host)
  *
  * Conventions
  *   - Tensors are caller-owned DEVICE buffers, time-major: row = b*T + t, channels contiguous.
@@ -170,6 +172,26 @@ svc_status svc_diffsvc_eps(svc_ctx* ctx, const float* cond, const float* x, int 
    mel_denorm_out (optional, f32 [B*T][n_mel]) receives the de-normalised mel. */
 svc_status svc_bigvgan(svc_ctx* ctx, const float* x0, int B, int T, const int32_t* frames, float* wav,
                        float* mel_denorm_out, void* stream);
+
+/* host-only: samples per output row for a batch whose longest utterance has n_samples:
+   n_samples + 2 * (add_silence ? fs / 20 : 0); -1 for n_samples < 0 or fs < 1 */
+int64_t svc_pcm16_len(int64_t n_samples, int fs, int add_silence);
+
+/* A16: utils/util.py:20-37 save_audio's sample conversion. wav f32 [B][S] -> pcm int16 [B][svc_pcm16_len(S, fs,
+   add_silence)]: per utterance, peak = max |x|, x * (float)(volume_peak / peak) when turn_up, fs / 20 zeros before and
+   after when add_silence, then clip(round_half_even(x * 32768), -32768, 32767): bit for bit the host path's samples
+   (audio.to_pcm16, the project's pinned restatement of the reference function) for finite input.
+   utt_samples (host int64 [B] or NULL = S each, 0 <= n_b <= S): ragged batch, see "Ragged batches"; utterance b's row
+   is [silence | its n_b samples | silence | zeros to the row's end], and only its own n_b samples enter its peak.
+   peak_out: optional device f32 [B], each utterance's max |x|.
+   pcm must not alias wav; wav needs 4-byte and pcm 2-byte alignment only. The context need not be finalized. The
+   length table goes through a ring of this entry point's own, so the call may run on any stream.
+   Two differences from the reference function:
+     - a silent or empty utterance (peak 0): the reference divides by zero (ZeroDivisionError); here its row is zeros
+       and its peak_out is 0;
+     - non-finite input is the caller's error and gives undefined samples (as for svc_whisper_encode). */
+svc_status svc_pcm16(svc_ctx* ctx, const float* wav, int B, int64_t S, const int64_t* utt_samples, int fs,
+                     int add_silence, int turn_up, double volume_peak, void* pcm, float* peak_out, void* stream);
 
 /* ---------------- op-level entry points (used by the parity tests; weights are unpacked f32 device arrays) */
 /* y[B*T_out][Cout] = conv1d(x[B*T_in][Cin]) ; w [Cout][Cin][k] ; act 0 none / 1 gelu / 2 relu */

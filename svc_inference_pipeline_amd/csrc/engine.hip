@@ -148,6 +148,9 @@ int pyin_tables(double sr, double fmin, double fmax, int frame_length, int win_l
 int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, const int64_t* nvalid_host, double sr,
             double fmin, double fmax, int frame_length, int win_length, int hop, int F, double* f0, void* ws,
             size_t ws_bytes, const double* tables_dev, hipStream_t s);
+size_t pcm16_table_bytes(int B);
+int pcm16(const float* wav, int B, int64_t S, void* table, int64_t max_nb, int sil, int64_t L, int turn_up,
+          double volume_peak, int16_t* pcm, float* peak_out, int need_peak, hipStream_t s);
 
 // ---------------------------------------------------------------------------- host helpers
 static std::vector<float> slaney_mel(int sr, int n_fft, int n_mels, double f_lo, double f_hi) {
@@ -436,6 +439,7 @@ struct svc_ctx {
   Tuning tune, tune0;  // kernel switches (tune0: their values at creation, for "tune.reset")
   // ragged-batch length tables, one ring per stage (the feature stages run on their own stream)
   StageRing lens_feat, lens_main;
+  StageRing lens_pcm;  // svc_pcm16: the length table and, behind it in the same slot, the zeroed peak scratch
   std::map<std::string, Param> params;
   std::map<std::string, double> cfg;
   bool finalized = false;
@@ -1527,6 +1531,7 @@ svc_status svc_ctx_destroy(svc_ctx* c) {
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   c->lens_feat.release();
   c->lens_main.release();
+  c->lens_pcm.release();
   delete c;
   return SVC_OK;
 }
@@ -2817,6 +2822,34 @@ svc_status svc_bigvgan(svc_ctx* c, const float* x0, int B, int T, const int32_t*
     }
   }
   return (tv && mel_out) ? zero_tail_rows(mel_out, B, T, nm, tv, s) : SVC_OK;
+}
+
+// ---------------------------------------------------------------------------- 16-bit PCM (A16)
+svc_status svc_pcm16(svc_ctx* c, const float* wav, int B, int64_t S, const int64_t* utt_samples, int fs,
+                     int add_silence, int turn_up, double volume_peak, void* pcm, float* peak_out, void* stream) {
+  SVC_REQUIRE(c, "pcm16: null context");
+  SVC_REQUIRE(wav && pcm, "pcm16: null %s", wav ? "pcm" : "wav");
+  SVC_REQUIRE(B >= 1 && S >= 1, "pcm16: B=%d S=%lld", B, (long long)S);
+  SVC_REQUIRE(fs >= 1, "pcm16: fs=%d", fs);
+  SVC_REQUIRE(!turn_up || volume_peak > 0.0, "pcm16: volume_peak %g (must be positive with turn_up)", volume_peak);
+  // one staged table (pcm16.hip): int64 n[B], then the peak scratch, whose zeros the same stream-ordered copy writes
+  std::vector<char> buf(pcm16_table_bytes(B), 0);
+  int64_t* nv = reinterpret_cast<int64_t*>(buf.data());
+  int64_t max_nb = 0;
+  for (int b = 0; b < B; ++b) {
+    nv[b] = utt_samples ? utt_samples[b] : S;
+    SVC_REQUIRE(nv[b] >= 0 && nv[b] <= S, "pcm16: utterance %d: %lld samples (batch length %lld)", b, (long long)nv[b],
+                (long long)S);
+    max_nb = std::max(max_nb, nv[b]);
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int sil = add_silence ? fs / 20 : 0;
+  RingRetire retire_(c->lens_pcm, s);
+  void* dev = nullptr;
+  if (int st = c->lens_pcm.put(buf.data(), buf.size(), s, &dev)) return st;
+  return pcm16(wav, B, S, dev, max_nb, sil, S + 2 * (int64_t)sil, turn_up ? 1 : 0, volume_peak,
+               reinterpret_cast<int16_t*>(pcm), peak_out, (turn_up || peak_out) ? 1 : 0, s);
 }
 
 // ---------------------------------------------------------------------------- op-level (tests)

@@ -44,8 +44,9 @@ def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckp
 
 
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                 f0_method="parselmouth"):
-    """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T)."""
+                 f0_method="parselmouth", pcm16=False):
+    """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
+    the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16)."""
     wav24 = A.load_audio(wav_path, cfg.fs, device=device)          # utils/audio.py:10-55
     if wav24 is None:
         raise A.AudioError(f"{wav_path}: non-finite samples")
@@ -56,14 +57,16 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
     singer = torch.tensor([int(singers[singer_name])], dtype=torch.int32, device=device)  # utils/util.py:49-54
     utt = torch.zeros(1, dtype=torch.int32, device=device)
     res = SVCPipeline(engine, f0_method=f0_method).convert(wav24[None].contiguous(), wav16[None].contiguous(), singer,
-                                      fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=utt)
-    return res.wav[0].cpu().numpy(), res.mel.shape[1]
+                                      fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=utt,
+                                      pcm16=pcm16)
+    return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                  f0_method="parselmouth"):
+                  f0_method="parselmouth", pcm16=False):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
-    list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result."""
+    list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
+    pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
@@ -76,9 +79,10 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
         w16.append(A.load_whisper_audio(p, device=device))
     sid = int(singers[singer_name])
     wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), fast_inference=fast_inference,
-                                            speedup=speedup, seed=seed)
+                                            speedup=speedup, seed=seed, pcm16=pcm16)
     hop = cfg.hop_length
-    return [(w.cpu().numpy(), int(w.shape[0]) // hop) for w in wavs]
+    sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
+    return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
 
 
 def main(argv=None):
@@ -113,15 +117,15 @@ def main(argv=None):
     dev = f"cuda:{args.device}"
     if len(args.wav) == 1:
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
-                                f0_method=args.f0_method)]
+                                f0_method=args.f0_method, pcm16=True)]
     else:
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
-                                f0_method=args.f0_method)
+                                f0_method=args.f0_method, pcm16=True)
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
-    for path, (wav, _) in zip(args.wav, results):
+    for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU
         out = args.out or os.path.join("gen", f"{os.path.splitext(os.path.basename(path))[0]}_{args.singer}.wav")
-        A.save_audio(out, wav, cfg.fs)
+        A.write_wav_pcm16(out, pcm, cfg.fs)
         print("Saving", out, flush=True)
     engine.close()
     return 0

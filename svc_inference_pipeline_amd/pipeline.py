@@ -7,6 +7,7 @@
     y_pred = svc_model_inference(...)                   infer.py:79   -> condition + diffsvc_sample
     y_pred = denormalize_mel_channel(y_pred, cfg)       infer.py:80   -> fused into bigvgan
     audio = synthesis_audios(...)                       infer.py:86   -> bigvgan (Generator, trim, fade)
+    save_audio(save_path, audio, cfg.fs)                infer.py:90   -> pcm16 (with pcm16=True; the file: audio.py)
 
 Inputs are device tensors of B equal-length utterances (24 kHz f32 and the 16 kHz int16-quantised
 copy Whisper consumes); every stage runs in libsvc_hip.so on the current stream.
@@ -39,6 +40,7 @@ class ConvertResult:
     mel: torch.Tensor        # f32 [B, T, n_mels] source log-mel
     f0: torch.Tensor         # f64 [B, T] pitch-shifted F0
     x0: torch.Tensor         # f32 [B, T, n_mel] normalised mel from the sampler
+    pcm: torch.Tensor = None  # int16 [B, T*hop + 2*(fs//20)] save_audio's samples of wav (convert(pcm16=True) only)
 
 
 class SVCPipeline:
@@ -117,14 +119,16 @@ class SVCPipeline:
         return self._side
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
-                noise=None, f0=None, wav16_float=None):
+                noise=None, f0=None, wav16_float=None, pcm16=False):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
-        Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified)."""
+        Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
+        save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`."""
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
-                                 wav16_float)
+                                 wav16_float, pcm16)
 
-    def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float):
+    def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
+                 pcm16=False):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -149,10 +153,10 @@ class SVCPipeline:
         x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, x_T=x_T, noise=noise, seed=seed,
                               utt_ids=utt_ids)
         wav = e.bigvgan(x0)
-        return ConvertResult(wav=wav, mel=mel, f0=f0, x0=x0)
+        return ConvertResult(wav=wav, mel=mel, f0=f0, x0=x0, pcm=e.pcm16(wav) if pcm16 else None)
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                     utt_ids=None, bucketed=False):
+                     utt_ids=None, bucketed=False, pcm16=False):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -160,14 +164,17 @@ class SVCPipeline:
 
         Default: ONE padded batch with per-utterance lengths (convert_ragged): every kernel that looks across time
         (STFT, Praat frames, convolutions, anti-aliased activations, fade-out) stops at each utterance's own end.
-        bucketed=True instead runs one batch per distinct length."""
+        bucketed=True instead runs one batch per distinct length.
+        pcm16=True: each waveform comes back as save_audio's samples instead, int16 [T_i*hop + 2*(fs//20)]
+        (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak)."""
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
             raise ValueError("convert_many: wavs24, wavs16, singers (and wavs16_float) must have one entry per utterance")
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
         if not bucketed:
             return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float,
-                                       fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=ids)
+                                       fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=ids,
+                                       pcm16=pcm16)
         buckets = {}
         for i in range(n):
             key = (int(wavs24[i].shape[-1]), int(wavs16[i].shape[-1]),
@@ -183,9 +190,9 @@ class SVCPipeline:
             sing = torch.tensor([int(singers[i]) for i in idx], device=dev, dtype=torch.int32)
             uid = torch.tensor([ids[i] for i in idx], device=dev, dtype=torch.int32)
             res = self.convert(w24, w16, sing, fast_inference=fast_inference, speedup=speedup, seed=seed,
-                               utt_ids=uid, wav16_float=w16f)
+                               utt_ids=uid, wav16_float=w16f, pcm16=pcm16)
             for j, i in enumerate(idx):
-                out[i] = res.wav[j]
+                out[i] = res.pcm[j] if pcm16 else res.wav[j]
         return out
 
     @staticmethod
@@ -237,14 +244,17 @@ class SVCPipeline:
         return out
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                       utt_ids=None):
+                       utt_ids=None, pcm16=False):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
-        -> list of waveforms f32 [T_b * hop]."""
+        -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
+        [T_b * hop + 2 * (fs // 20)] (svc_pcm16 with the same lengths)."""
         with self.engine.lock:
-            return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids)
+            return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
+                                        pcm16)
 
-    def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids):
+    def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
+                        pcm16=False):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -270,4 +280,8 @@ class SVCPipeline:
         x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=uid, frames=T_b)
         wav = e.bigvgan(x0, frames=T_b)
         hop = e.cfg.hop_length
+        if pcm16:
+            pcm = e.pcm16(wav, n_samples=[t * hop for t in T_b])
+            sil2 = pcm.shape[1] - wav.shape[1]  # both silences
+            return [pcm[i, :T_b[i] * hop + sil2] for i in range(n)]
         return [wav[i, :T_b[i] * hop] for i in range(n)]

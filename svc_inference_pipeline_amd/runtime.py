@@ -330,3 +330,20 @@ class SVCEngine:
         _lib.call("svc_bigvgan", self._ctx, _ptr(x0.contiguous()), B, T, _host_lengths(frames, B, ctypes.c_int32),
                   _ptr(wav), _ptr(mel), _stream())
         return (wav, mel) if return_mel else wav
+
+    def pcm16(self, wav, n_samples=None, add_silence=True, turn_up=True, volume_peak=0.9, return_peak=False):
+        """save_audio's sample conversion (utils/util.py:20-37; audio.to_pcm16 per utterance, bit for bit) on the
+        device: wav f32 [B, S] -> int16 [B, S + 2 * sil], sil = fs // 20 with add_silence else 0. n_samples (ragged
+        batch, host ints [B], 0 <= n_b <= S): utterance b is wav[b, :n_samples[b]], normalised by its own peak; its
+        row is [sil zeros | n_b samples | sil zeros | zeros]. A silent or empty utterance gives zeros and peak 0
+        (to_pcm16 raises ZeroDivisionError). return_peak: also the f32 [B] peaks max |x|."""
+        if wav.dim() != 2 or wav.dtype != torch.float32:
+            raise ValueError("pcm16: wav must be f32 [B, S]")
+        B, S = wav.shape
+        L = int(_lib.load().svc_pcm16_len(S, int(self.cfg.fs), 1 if add_silence else 0))
+        pcm = torch.empty(B, L, device=wav.device, dtype=torch.int16)
+        peak = torch.empty(B, device=wav.device, dtype=torch.float32) if return_peak else None
+        _lib.call("svc_pcm16", self._ctx, _ptr(wav), B, S, _host_lengths(n_samples, B, ctypes.c_int64),
+                  int(self.cfg.fs), 1 if add_silence else 0, 1 if turn_up else 0, float(volume_peak), _ptr(pcm),
+                  _ptr(peak), _stream())
+        return (pcm, peak) if return_peak else pcm

@@ -49,7 +49,9 @@ class _Request:
 
 class SVCServer:
     def __init__(self, pipeline: SVCPipeline, max_batch=32, max_wait_s=0.02, length_ratio=2.0, fast_inference=True,
-                 speedup=10, seed=0):
+                 speedup=10, seed=0, pcm16=False):
+        """pcm16=True: each future resolves to save_audio's samples of its waveform, int16 [T * hop + 2 * (fs // 20)]
+        (convert_ragged(pcm16=True): half the bytes to copy back, no host normalisation), instead of the f32 waveform."""
         if max_batch < 1 or max_wait_s < 0 or length_ratio < 1.0:
             raise ValueError("SVCServer: max_batch >= 1, max_wait_s >= 0, length_ratio >= 1")
         self.pipeline = pipeline
@@ -57,6 +59,8 @@ class SVCServer:
         self.max_wait_s = float(max_wait_s)
         self.length_ratio = float(length_ratio)
         self.kw = dict(fast_inference=fast_inference, speedup=speedup, seed=seed)
+        if pcm16:
+            self.kw["pcm16"] = True
         cfg = pipeline.engine.cfg
         self._frames = lambda n: mel_frames(n, cfg.n_fft, cfg.hop_length)
         self._ids = itertools.count()
@@ -70,7 +74,7 @@ class SVCServer:
 
     def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None) -> Future:
         """Queue one utterance (device tensors: 24 kHz f32 [N], 16 kHz [N16], optional float 16 kHz for
-        ContentVec) -> Future resolving to its waveform f32 [T * hop]."""
+        ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True)."""
         n = int(wav24.shape[-1])
         if n < 1 or int(wav16.shape[-1]) < 1:
             raise ValueError("SVCServer.submit: empty audio")
