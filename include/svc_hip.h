@@ -13,6 +13,9 @@
  *   svc_diffsvc_sample  <- modules/diffsvcrepo_inference.py:154-240 svc_model_inference (DDPM or PLMS)
  *   svc_bigvgan         <- utils/acoustic_feature_extraction.py:83-97 denormalize_mel_channel
  *                          + modules/bigvgan_inference.py:29-44 synthesis_audios (Generator + trim + fade)
+ *   svc_load_pcm        <- utils/audio.py:10-55 load_audio_torch + utils/whisper_extractor/audio.py:22-49 load_audio
+ *                          (sample decode, normalisation, mono mix and both resamplings of a ragged batch of wav
+ *                          payloads; the RIFF header is parsed on the host)
  *   svc_pcm16           <- utils/util.py:20-37 save_audio (peak normalisation, silence, 16-bit samples; the file
  *                          itself is written on the host)
  *
@@ -172,6 +175,38 @@ svc_status svc_diffsvc_eps(svc_ctx* ctx, const float* cond, const float* x, int 
    mel_denorm_out (optional, f32 [B*T][n_mel]) receives the de-normalised mel. */
 svc_status svc_bigvgan(svc_ctx* ctx, const float* x0, int B, int T, const int32_t* frames, float* wav,
                        float* mel_denorm_out, void* stream);
+
+/* sample formats of a wav payload (little-endian, channels interleaved): PCM unsigned 8-bit, signed 16 / 24 / 32-bit,
+   IEEE float 32 / 64-bit */
+#define SVC_PCM_U8 0
+#define SVC_PCM_S16 1
+#define SVC_PCM_S24 2
+#define SVC_PCM_S32 3
+#define SVC_PCM_F32 4
+#define SVC_PCM_F64 5
+
+/* A1: the input end for a ragged batch of B wav files, replacing utils/audio.py:10-55 load_audio_torch (-> y_src) and
+   utils/whisper_extractor/audio.py:22-49 load_audio (-> y_mono) for wav input: at most three launches whatever B is.
+   raw: ONE device byte buffer holding the files' data-chunk payloads, utterance b's at raw + byte_off[b] (any byte
+   alignment), n_frames[b] frames of channels[b] (1..8) interleaved samples of format[b] (SVC_PCM_*) at sr_in[b] Hz.
+   The five tables are HOST arrays [B], staged through a ring of this entry point's own (any stream).
+   y_src f32 [B][S_src] (or NULL): row b = channel 0 as float, divided by 1, 2^15 + 1 or 2^31 + 1 by its peak class
+   (peak > 1.01, > 2^15; float formats only), resampled to sr_src (rows already at sr_src are not filtered): its first
+   svc_resample_len(n_frames[b], sr_in[b], sr_src) samples, zeros after them to S_src.
+   y_mono f32 [B][S_mono] (or NULL): row b = the mean over the channels (numpy's summation order, in f64) as float,
+   resampled to sr_mono (always through the filter) and rounded to the int16 grid (svc_resample's quantize16), zeros
+   after its svc_resample_len(n_frames[b], sr_in[b], sr_mono) samples.
+   Each row is bit for bit what audio.load_audio / audio.load_whisper_audio give for that file alone (svc_resample's
+   filter, index arithmetic and summation order). An empty utterance gives rows of zeros.
+   info int32 [B] (device, or NULL): bits 0-1 the peak class (0, 1, 2), bit 2 set when the source row holds a
+   non-finite sample (NaN, Inf, or a finite f64 beyond the f32 range; the mono row is not examined).
+   SVC_ERR_INVALID before any HIP call: a null pointer (both outputs NULL included), B < 1, channels outside 1..8, an
+   unknown format, a rate < 1, a negative length or offset, S_src / S_mono < 1 or shorter than the longest row, a rate
+   ratio whose filter span exceeds the kernel's tile (down / up beyond ~400). The context need not be finalized. */
+svc_status svc_load_pcm(svc_ctx* ctx, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+                        const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,
+                        int64_t S_src, float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info,
+                        void* stream);
 
 /* host-only: samples per output row for a batch whose longest utterance has n_samples:
    n_samples + 2 * (add_silence ? fs / 20 : 0); -1 for n_samples < 0 or fs < 1 */

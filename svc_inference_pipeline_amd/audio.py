@@ -4,6 +4,8 @@
     load_audio(file, sr=16000)        utils/whisper_extractor/audio.py:22-49 (ffmpeg s16le decode)
                                                                       -> load_whisper_audio
     save_audio(path, waveform, fs)    utils/util.py:20-37              -> save_audio
+    both loaders for a batch of files                                 -> load_batch (parse_wav on the host, one
+                                                                         svc_load_pcm call on the GPU)
 
 The reference reads wavs with soundfile, resamples with librosa (soxr) and decodes Whisper's 16 kHz input with
 an ffmpeg subprocess; none of the three is in this image. Here a RIFF/WAVE reader gives soundfile's float
@@ -12,6 +14,7 @@ conversion (PCM int / 2^(bits-1), IEEE float as stored), and resampling runs in 
 against soxr / ffmpeg's swresample). Only WAV input is supported (the reference's non-wav branch uses
 librosa.load).
 """
+import collections
 import ctypes
 import os
 import struct
@@ -73,6 +76,49 @@ def read_wav(path):
     return x.reshape(n, ch), sr
 
 
+# sample-format codes of svc_load_pcm (include/svc_hip.h SVC_PCM_*) by (format tag, bits per sample)
+PCM_FORMATS = {(1, 8): 0, (1, 16): 1, (1, 24): 2, (1, 32): 3, (3, 32): 4, (3, 64): 5}
+PCM_DTYPES = ("u1", "<i2", None, "<i4", "<f4", "<f8")  # numpy dtype of a format code's samples (24-bit: none)
+
+# a parsed wav: format code, channels, sample rate, frames, and a view of the data chunk's first frames * align bytes
+WavInfo = collections.namedtuple("WavInfo", "format channels sr n_frames payload name")
+
+
+def parse_wav(src, name=None):
+    """RIFF/WAVE header of `src` (a path, bytes or a memoryview) -> WavInfo, without touching the samples: the payload
+    is a zero-copy view into the file's bytes. Accepts and rejects exactly what read_wav does (the same chunk walk:
+    odd-sized chunks padded, the last fmt / data chunk wins, WAVE_FORMAT_EXTENSIBLE by its sub-format)."""
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data, path = memoryview(src).cast("B"), name if name is not None else "<bytes>"
+    else:
+        path = src if name is None else name
+        with open(src, "rb") as fh:
+            data = memoryview(fh.read())
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+        raise AudioError(f"{path}: not a RIFF/WAVE file")
+    pos, fmt, payload = 12, None, None
+    while pos + 8 <= len(data):
+        cid, size = bytes(data[pos:pos + 4]), struct.unpack("<I", data[pos + 4:pos + 8])[0]
+        body = data[pos + 8:pos + 8 + size]
+        if cid == b"fmt ":
+            tag, ch, sr, _, align, bits = struct.unpack("<HHIIHH", body[:16])
+            if tag == 0xFFFE and len(body) >= 26:
+                tag = struct.unpack("<H", body[24:26])[0]
+            fmt = (tag, ch, sr, align, bits)
+        elif cid == b"data":
+            payload = body
+        pos += 8 + size + (size & 1)
+    if fmt is None or payload is None:
+        raise AudioError(f"{path}: missing fmt or data chunk")
+    tag, ch, sr, align, bits = fmt
+    if ch < 1 or align != ch * bits // 8:
+        raise AudioError(f"{path}: unsupported layout ({ch} channels, block align {align}, {bits} bits)")
+    n = len(payload) // align
+    if (tag, bits) not in PCM_FORMATS:
+        raise AudioError(f"{path}: unsupported sample format (tag {tag}, {bits} bits)")
+    return WavInfo(PCM_FORMATS[(tag, bits)], ch, sr, n, payload[:n * align], str(path))
+
+
 def _normalise(audio):
     """utils/audio.py:31-45: float data scaled by 1, 2^15+1 or 2^31+1 by its peak, then float32."""
     mx = max(float(np.amax(audio)), float(-np.amin(audio))) if audio.size else 0.0
@@ -116,6 +162,46 @@ def load_whisper_audio(path, sr=WHISPER_SR, device="cuda"):
     audio, sr_in = read_wav(path)
     mono = audio.mean(axis=1).astype(np.float32)
     return resample(mono, sr_in, sr, device=device, quantize16=True)
+
+
+def load_batch(sources, fs, engine, on_error="raise"):
+    """load_audio and load_whisper_audio for a batch of wav files (paths, bytes or memoryviews; or WavInfo already
+    parsed) in ONE device stage: headers on the host, then one upload and one svc_load_pcm call
+    (SVCEngine.load_pcm) -> (wavs24, wavs16), lists of per-utterance row views of the two padded batches (what
+    SVCPipeline.convert_ragged takes), each row bit for bit the per-file function's result.
+    AudioError naming the source: a file of <= 2 frames (load_audio), or one with non-finite samples (where load_audio
+    returns None and infer.py raises). on_error="return": nothing is raised for a bad file; the result is
+    (wavs24, wavs16, errors) with None for it in both lists and its exception in errors (a dict by position); the other
+    files are decoded as usual."""
+    infos, errors = [], {}
+    for i, src in enumerate(sources):
+        try:
+            info = src if isinstance(src, WavInfo) else parse_wav(src, None if isinstance(src, (str, os.PathLike))
+                                                                else f"<source {i}>")
+            if info.n_frames <= 2:
+                raise AudioError(f"{info.name}: {info.n_frames} samples")
+            if info.channels > 8:
+                raise AudioError(f"{info.name}: {info.channels} channels (at most 8)")
+            infos.append((i, info))
+        except (AudioError, struct.error, OSError) as exc:
+            if on_error == "raise":
+                raise
+            errors[i] = exc
+    w24, w16 = [None] * len(sources), [None] * len(sources)
+    if infos:
+        y24, y16, n24, n16, flags = engine.load_pcm([info for _, info in infos], fs)
+        # integer samples cannot be non-finite: the flags are fetched only when some file holds floats
+        bits = flags.cpu().tolist() if any(info.format >= 4 for _, info in infos) else [0] * len(infos)
+        for j, (i, info) in enumerate(infos):
+            if bits[j] & 4:
+                errors[i] = AudioError(f"{info.name}: non-finite samples")
+                continue
+            w24[i], w16[i] = y24[j, :n24[j]], y16[j, :n16[j]]
+    if on_error == "raise":
+        if errors:
+            raise errors[min(errors)]
+        return w24, w16
+    return w24, w16, errors
 
 
 def to_pcm16(waveform, fs, add_silence=True, turn_up=True, volume_peak=0.9):

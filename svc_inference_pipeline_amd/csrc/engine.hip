@@ -151,6 +151,9 @@ int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, cons
 size_t pcm16_table_bytes(int B);
 int pcm16(const float* wav, int B, int64_t S, void* table, int64_t max_nb, int sil, int64_t L, int turn_up,
           double volume_peak, int16_t* pcm, float* peak_out, int need_peak, hipStream_t s);
+int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+             const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
+             float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info, hipStream_t s);
 
 // ---------------------------------------------------------------------------- host helpers
 static std::vector<float> slaney_mel(int sr, int n_fft, int n_mels, double f_lo, double f_hi) {
@@ -440,6 +443,7 @@ struct svc_ctx {
   // ragged-batch length tables, one ring per stage (the feature stages run on their own stream)
   StageRing lens_feat, lens_main;
   StageRing lens_pcm;  // svc_pcm16: the length table and, behind it in the same slot, the zeroed peak scratch
+  StageRing lens_load;  // svc_load_pcm: the utterance and plan tables and the zeroed peak scratch (load_pcm.hip)
   std::map<std::string, Param> params;
   std::map<std::string, double> cfg;
   bool finalized = false;
@@ -1532,6 +1536,7 @@ svc_status svc_ctx_destroy(svc_ctx* c) {
   c->lens_feat.release();
   c->lens_main.release();
   c->lens_pcm.release();
+  c->lens_load.release();
   delete c;
   return SVC_OK;
 }
@@ -2850,6 +2855,17 @@ svc_status svc_pcm16(svc_ctx* c, const float* wav, int B, int64_t S, const int64
   if (int st = c->lens_pcm.put(buf.data(), buf.size(), s, &dev)) return st;
   return pcm16(wav, B, S, dev, max_nb, sil, S + 2 * (int64_t)sil, turn_up ? 1 : 0, volume_peak,
                reinterpret_cast<int16_t*>(pcm), peak_out, (turn_up || peak_out) ? 1 : 0, s);
+}
+
+// ---------------------------------------------------------------------------- wav payloads -> the input batches (A1)
+svc_status svc_load_pcm(svc_ctx* c, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+                        const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,
+                        int64_t S_src, float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info,
+                        void* stream) {
+  SVC_REQUIRE(c, "load_pcm: null context");
+  // the context is read only once the arguments have passed (load_pcm.hip checks them before any HIP call)
+  return load_pcm(&c->lens_load, &c->device, raw, B, byte_off, n_frames, format, channels, sr_in, sr_src, S_src, y_src,
+                  sr_mono, S_mono, y_mono, info, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------- op-level (tests)

@@ -104,17 +104,50 @@ static ResamplePlan design_plan(int sr_in, int sr_out, std::vector<double>& hp) 
   return p;
 }
 
-static const ResamplePlan* get_plan(int sr_in, int sr_out) {
+// A cached plan: resample_kernel's (taps in design order) and, for load_pcm.hip, the same taps phase-major,
+// hpm[k0 * per_phase + r] = h[k0 + up * r], zero where k0 + up * r >= taps (never read: r_hi stops before it)
+struct CachedPlan {
+  ResamplePlan plan;
+  double* hpm = nullptr;
+  int per_phase = 0;
+};
+
+static const CachedPlan* get_cached_plan(int sr_in, int sr_out) {
   static std::mutex mu;
-  static std::map<std::pair<int, int>, ResamplePlan> plans;
+  static std::map<std::pair<int, int>, CachedPlan> plans;
   std::lock_guard<std::mutex> lock(mu);
   auto it = plans.find({sr_in, sr_out});
   if (it != plans.end()) return &it->second;
   std::vector<double> hp;
-  ResamplePlan p = design_plan(sr_in, sr_out, hp);
+  CachedPlan c;
+  ResamplePlan& p = c.plan;
+  p = design_plan(sr_in, sr_out, hp);
+  c.per_phase = (p.taps - 1) / p.up + 1;
+  std::vector<double> pm((size_t)p.up * c.per_phase, 0.0);
+  for (int k = 0; k < p.taps; ++k) pm[(size_t)(k % p.up) * c.per_phase + k / p.up] = hp[k];
   if (hipMalloc(&p.h, hp.size() * sizeof(double)) != hipSuccess) return nullptr;
   if (hipMemcpy(p.h, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-  return &(plans[{sr_in, sr_out}] = p);
+  if (hipMalloc(&c.hpm, pm.size() * sizeof(double)) != hipSuccess) return nullptr;
+  if (hipMemcpy(c.hpm, pm.data(), pm.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+  return &(plans[{sr_in, sr_out}] = c);
+}
+
+static const ResamplePlan* get_plan(int sr_in, int sr_out) {
+  const CachedPlan* c = get_cached_plan(sr_in, sr_out);
+  return c ? &c->plan : nullptr;
+}
+
+int get_plan_pm(int sr_in, int sr_out, const double** hpm, int* up, int* down, int* pre_remove, int* taps,
+                int* per_phase) {
+  const CachedPlan* c = get_cached_plan(sr_in, sr_out);
+  if (!c) return -1;
+  *hpm = c->hpm;
+  *up = c->plan.up;
+  *down = c->plan.down;
+  *pre_remove = c->plan.pre_remove;
+  *taps = c->plan.taps;
+  *per_phase = c->per_phase;
+  return 0;
 }
 
 }  // namespace svc

@@ -47,10 +47,8 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
                  f0_method="parselmouth", pcm16=False):
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
     the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16)."""
-    wav24 = A.load_audio(wav_path, cfg.fs, device=device)          # utils/audio.py:10-55
-    if wav24 is None:
-        raise A.AudioError(f"{wav_path}: non-finite samples")
-    wav16 = A.load_whisper_audio(wav_path, device=device)          # whisper_extractor/audio.py:22-49
+    # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
+    (wav24,), (wav16,) = A.load_batch([wav_path], cfg.fs, engine)
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
@@ -70,13 +68,7 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
-    w24, w16 = [], []
-    for p in wav_paths:
-        w = A.load_audio(p, cfg.fs, device=device)
-        if w is None:
-            raise A.AudioError(f"{p}: non-finite samples")
-        w24.append(w)
-        w16.append(A.load_whisper_audio(p, device=device))
+    w24, w16 = A.load_batch(list(wav_paths), cfg.fs, engine)  # all files decoded and resampled in one device stage
     sid = int(singers[singer_name])
     wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), fast_inference=fast_inference,
                                             speedup=speedup, seed=seed, pcm16=pcm16)

@@ -253,6 +253,14 @@ class SVCPipeline:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
                                         pcm16)
 
+    def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False):
+        """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
+        batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it."""
+        from . import audio as A
+        wavs24, wavs16 = A.load_batch(sources, self.engine.cfg.fs, self.engine)
+        return self.convert_ragged(wavs24, wavs16, singers, fast_inference=fast_inference, speedup=speedup, seed=seed,
+                                   utt_ids=utt_ids, pcm16=pcm16)
+
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
                         pcm16=False):
         e = self.engine

@@ -331,6 +331,37 @@ class SVCEngine:
                   _ptr(wav), _ptr(mel), _stream())
         return (wav, mel) if return_mel else wav
 
+    def load_pcm(self, infos, fs=None, sr_mono=16000):
+        """The input end for a batch of parsed wavs (audio.WavInfo: format code, channels, rate, frames, payload view):
+        one host concatenation of the payloads, one upload, one svc_load_pcm call -> (y_src f32 [B, S_src] at `fs`
+        (default: the config's), y_mono f32 [B, S_mono] at sr_mono on the int16 grid, n_src, n_mono (host ints [B]: each
+        row's own samples, zeros after them), info int32 [B] on the device (bits 0-1 the normalisation class, bit 2
+        non-finite source samples)). Row b is bit for bit audio.load_audio / audio.load_whisper_audio of that file."""
+        fs = int(self.cfg.fs if fs is None else fs)
+        B = len(infos)
+        if B < 1:
+            raise ValueError("load_pcm: no utterances")
+        lib = _lib.load()
+        sizes = [len(i.payload) for i in infos]
+        offs = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+        host = np.empty(max(1, sum(sizes)), dtype=np.uint8)
+        for o, n, i in zip(offs.tolist(), sizes, infos):
+            host[o:o + n] = np.frombuffer(i.payload, dtype=np.uint8)
+        with self.lock:
+            dev = torch.device("cuda", self.device)
+            raw = torch.from_numpy(host).to(dev)
+            n_src = [int(lib.svc_resample_len(i.n_frames, i.sr, fs)) for i in infos]
+            n_mono = [int(lib.svc_resample_len(i.n_frames, i.sr, sr_mono)) for i in infos]
+            y_src = torch.empty(B, max(1, max(n_src)), device=dev, dtype=torch.float32)
+            y_mono = torch.empty(B, max(1, max(n_mono)), device=dev, dtype=torch.float32)
+            info = torch.empty(B, device=dev, dtype=torch.int32)
+            i64, i32 = ctypes.c_int64 * B, ctypes.c_int32 * B
+            _lib.call("svc_load_pcm", self._ctx, _ptr(raw), B, i64(*offs.tolist()), i64(*[i.n_frames for i in infos]),
+                      i32(*[i.format for i in infos]), i32(*[i.channels for i in infos]), i32(*[i.sr for i in infos]),
+                      fs, y_src.shape[1], _ptr(y_src), int(sr_mono), y_mono.shape[1], _ptr(y_mono), _ptr(info),
+                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        return y_src, y_mono, n_src, n_mono, info
+
     def pcm16(self, wav, n_samples=None, add_silence=True, turn_up=True, volume_peak=0.9, return_peak=False):
         """save_audio's sample conversion (utils/util.py:20-37; audio.to_pcm16 per utterance, bit for bit) on the
         device: wav f32 [B, S] -> int16 [B, S + 2 * sil], sil = fs // 20 with add_silence else 0. n_samples (ragged

@@ -6,6 +6,7 @@ and of any length; SVCServer turns that stream into ragged GPU batches:
     server = SVCServer(SVCPipeline(engine), max_batch=32, max_wait_s=0.02)
     fut = server.submit(wav24, wav16, singer_id)       # returns at once (concurrent.futures.Future)
     wav = fut.result()                                 # f32 [T * hop] on the GPU
+    fut = server.submit_file(wav_bytes_or_path, singer_id)   # a wav file: only its header is parsed here
     server.close()
 
 A worker thread takes the oldest pending request, adds the pending requests whose length is within `length_ratio` of
@@ -17,11 +18,13 @@ converting that clip alone with the same id, whatever it was batched with (tests
 Streams: submit() records an event on the caller's current stream, and the worker's stream waits for it before it
 reads the request's tensors, so inputs produced by kernels still in flight on the caller's stream are safe to
 submit. A result is a view into the batch's output, recorded for use on the submitting stream (record_stream), and
-the future resolves once it is complete. The engine's lock (SVCEngine.lock) serialises the worker's conversions with
+the future resolves once it is complete. File requests carry no tensors: the worker decodes all of a batch's files in
+one audio.load_batch (svc_load_pcm) on its own stream. The engine's lock (SVCEngine.lock) serialises the worker's conversions with
 any direct use of the same engine.
 """
 import collections
 import itertools
+import os
 import threading
 import time
 from concurrent.futures import Future
@@ -29,6 +32,8 @@ from dataclasses import dataclass, field
 
 import torch
 
+from . import _lib
+from . import audio as A
 from .pipeline import SVCPipeline
 from .runtime import mel_frames
 
@@ -45,6 +50,7 @@ class _Request:
     ready: object = None    # torch.cuda.Event recorded on the submitting stream (None on the CPU)
     stream: object = None   # the submitting stream
     future: Future = field(default_factory=Future)
+    file: object = None     # audio.WavInfo of a submit_file request (wav24 / wav16 are decoded by the worker)
 
 
 class SVCServer:
@@ -63,6 +69,7 @@ class SVCServer:
             self.kw["pcm16"] = True
         cfg = pipeline.engine.cfg
         self._frames = lambda n: mel_frames(n, cfg.n_fft, cfg.hop_length)
+        self._fs = getattr(cfg, "fs", None)  # the model rate file requests are resampled to
         self._ids = itertools.count()
         self._pending = []
         self._cv = threading.Condition()
@@ -92,6 +99,39 @@ class SVCServer:
             self._pending.append(req)
             self._cv.notify()
         return req.future
+
+    def submit_file(self, src, singer, utt_id=None) -> Future:
+        """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
+        the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
+        the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
+        requests). A bad file (unreadable header, <= 2 frames, non-finite samples) fails its own future only."""
+        req = self._file_request(src, singer, utt_id)
+        if req.future.done():
+            return req.future
+        if torch.cuda.is_available():
+            req.stream = torch.cuda.current_stream(self._device)
+        with self._cv:
+            if self._closed:
+                raise RuntimeError("SVCServer.submit_file: the server is closed")
+            self._pending.append(req)
+            self._cv.notify()
+        return req.future
+
+    def _file_request(self, src, singer, utt_id=None):
+        """The request of one wav file from its header alone: frames = mel_frames(svc_resample_len(file frames, file
+        rate, fs)), nothing decoded. A file that cannot be queued comes back with its future already failed."""
+        req = _Request(wav24=None, wav16=None, singer=int(singer),
+                       utt_id=next(self._ids) if utt_id is None else int(utt_id), t_submit=time.monotonic())
+        try:
+            info = A.parse_wav(src, None if isinstance(src, (str, os.PathLike)) else f"<request {req.utt_id}>")
+            if info.n_frames <= 2:
+                raise A.AudioError(f"{info.name}: {info.n_frames} samples")
+        except Exception as exc:  # noqa: BLE001 - the caller sees it through the future, like a decode failure
+            req.future.set_exception(exc)
+            return req
+        req.file = info
+        req.frames = self._frames(int(_lib.load().svc_resample_len(info.n_frames, info.sr, int(self._fs))))
+        return req
 
     def close(self, wait=True):
         """Stop accepting requests; the worker finishes every queued request first."""
@@ -146,7 +186,27 @@ class SVCServer:
                 batch = self._take_batch()
             self._convert(batch)
 
+    def _decode_files(self, batch):
+        """Decode the batch's file requests in one load_batch; a file that fails resolves its own future with the error
+        and leaves the batch. -> the requests that go on."""
+        files = [r for r in batch if r.file is not None]
+        if not files:
+            return batch
+        try:
+            w24, w16, errors = A.load_batch([r.file for r in files], self._fs, self.pipeline.engine, on_error="return")
+        except Exception as exc:  # noqa: BLE001 - the decode itself failed: every file request of the batch
+            w24, w16, errors = [None] * len(files), [None] * len(files), {i: exc for i in range(len(files))}
+        for i, r in enumerate(files):
+            if i in errors:
+                r.future.set_exception(errors[i])
+            else:
+                r.wav24, r.wav16 = w24[i], w16[i]
+        return [r for r in batch if r.wav24 is not None]
+
     def _convert(self, batch):
+        batch = self._decode_files(batch)
+        if not batch:
+            return
         try:
             if torch.cuda.is_available():
                 work = torch.cuda.current_stream()
