@@ -9,6 +9,8 @@
  *   svc_pitch_shift     <- utils/acoustic_feature_extraction.py:48-52 pitch_shift
  *   svc_whisper_encode  <- utils/whisper.py:13-28 whisper_encoder (log_mel_spectrogram + AudioEncoder)
  *   svc_map_content     <- utils/whisper.py:31-81 get_mapped_whisper_features
+ *   svc_hubert_encode   <- utils/hubert.py:31-47 get_hubert_content (svc_hubert_encode_ragged: a ragged batch in one pass)
+ *   svc_map_content_ragged <- utils/hubert.py:83-134 get_mapped_features / utils/whisper.py:31-81, per utterance
  *   svc_condition       <- modules/encoder.py:165-201 EncoderFramework.forward
  *   svc_diffsvc_sample  <- modules/diffsvcrepo_inference.py:154-240 svc_model_inference (DDPM or PLMS)
  *   svc_bigvgan         <- utils/acoustic_feature_extraction.py:83-97 denormalize_mel_channel
@@ -38,9 +40,13 @@
  *     batch length. Each utterance is then computed exactly as a clip of its own length (its own reflect / zero /
  *     replicate padding, STFT frames, Praat frame grid, fade-out): outputs are bit-identical to converting it alone,
  *     and the rows past its end are written as zeros. Whisper needs no lengths: pad its 16 kHz input with zeros (as
- *     pad_or_trim does). The tables are staged to the device through a ring of 8 slots per stage group; a slot is
- *     reused only after every kernel of the call that read it has finished (its event is re-recorded on the call's
- *     stream after the call's last launch), so calls may use any streams.
+ *     pad_or_trim does). HuBERT / ContentVec does need them (its GroupNorm normalises over time, its positional
+ *     convolution reads past the end and its attention looks at every key): svc_hubert_encode_ragged takes
+ *     utt_samples (int64 [B], 16 kHz samples) and svc_map_content_ragged takes each utterance's source rows and mel
+ *     frames (int32 [B] each), so a ragged ContentVec batch is one encoder pass and one mapping launch. The tables
+ *     are staged to the device through a ring of 8 slots per stage group; a slot is reused only after every kernel of
+ *     the call that read it has finished (its event is re-recorded on the call's stream after the call's last
+ *     launch), so calls may use any streams.
  */
 #ifndef SVC_HIP_H
 #define SVC_HIP_H
@@ -132,11 +138,32 @@ svc_status svc_map_content(svc_ctx* ctx, const float* feats, int B, int src_rows
 svc_status svc_map_content_ex(svc_ctx* ctx, const float* feats, int B, int src_rows, int T, int D, int mode,
                               void* out_f16, int ld_out, void* stream);
 
+/* svc_map_content_ex for a ragged batch: utterance b maps its first utt_src_rows[b] (1..src_rows) rows of feats to
+   frames[b] (1..T) rows of out exactly as svc_map_content_ex maps a batch of that shape (mode 1: n_down =
+   utt_src_rows[b] * 15 / 8, and |frames[b] - n_down| > 3 is SVC_ERR_INVALID naming the utterance); its rows
+   frames[b] .. T-1 are zeros (columns 0..D-1; columns past D are not touched). Both tables are HOST int32 [B],
+   checked before any HIP call; NULL = src_rows / T for every utterance (both NULL: svc_map_content_ex). */
+svc_status svc_map_content_ragged(svc_ctx* ctx, const float* feats, int B, int src_rows, const int32_t* utt_src_rows,
+                                  int T, const int32_t* frames, int D, int mode, void* out_f16, int ld_out,
+                                  void* stream);
+
 /* A8 (variant): HuBERT/ContentVec content encoder, replacing utils/hubert.py:31-47 get_hubert_content
    (fairseq HubertModel.extract_features(output_layer = config "hubert.output_layer", default 9) + final_proj).
    wav16k [B][n_samples] f32 (librosa-loaded 16 kHz float audio, utils/hubert.py:55) -> feats
-   [B*svc_hubert_frames(n)][final_dim] f32. Parameters are added as "hubert." + fairseq state_dict keys. */
+   [B*svc_hubert_frames(n)][final_dim] f32. Parameters are added as "hubert." + fairseq state_dict keys.
+   Every utterance has the batch length n: the GroupNorm normalises over all its rows and the attention sees every
+   frame, so zero padding is NOT exact here (unlike Whisper); clips of different lengths go through
+   svc_hubert_encode_ragged below. */
 svc_status svc_hubert_encode(svc_ctx* ctx, const float* wav16k, int B, int64_t n_samples, float* feats, void* stream);
+/* The same for a ragged batch (see "Ragged batches"): utterance b is wav16k[b][0 .. utt_samples[b]), the rest of its
+   row is never read (it may hold anything). Its svc_hubert_frames(utt_samples[b]) rows of feats are bit-identical to
+   svc_hubert_encode on that clip alone: the GroupNorm statistics run over its own conv_layers[0] rows in the chunk
+   partition a clip of that length gets, the positional convolution sees zeros past its last frame, and the attention
+   stops at its last frame (queries and keys). Its remaining rows of feats (the batch stride stays
+   svc_hubert_frames(n_samples)) are zeros. utt_samples: HOST int64 [B], each 400 (one frame) .. n_samples, otherwise
+   SVC_ERR_INVALID before any HIP call; NULL = svc_hubert_encode. */
+svc_status svc_hubert_encode_ragged(svc_ctx* ctx, const float* wav16k, int B, int64_t n_samples,
+                                    const int64_t* utt_samples, float* feats, void* stream);
 /* frames of the conv feature extractor for n samples (499 for 160 000) */
 int64_t svc_hubert_frames(int64_t n_samples);
 svc_status svc_hubert_dims(svc_ctx* ctx, int* final_dim, int* embed_dim);
@@ -275,6 +302,12 @@ svc_status svc_op_activation1d_x16(const void* x16, int B, int L, int C, const f
 /* attention on f32 q,k,v [B*L][D] (already projected; scaled inside by dh^-1/4 each) -> out f32 [B*L][D] */
 svc_status svc_op_attention(const float* q, const float* k, const float* v, int B, int L, int D, float* out,
                             void* stream);
+/* the same with per-utterance lengths, as svc_hubert_encode_ragged runs it: lens HOST int32 [B], each 1..L
+   (otherwise SVC_ERR_INVALID before any HIP call; NULL = svc_op_attention). Utterance b attends over its first
+   lens[b] rows only and equals svc_op_attention on those rows at L = lens[b] bit for bit; rows >= lens[b] of q / k / v
+   are never read, and rows >= lens[b] of out are zeros. */
+svc_status svc_op_attention_ragged(const float* q, const float* k, const float* v, int B, int L, int D,
+                                   const int32_t* lens, float* out, void* stream);
 svc_status svc_op_layernorm(const float* x, const float* g, const float* b, int rows, int D, float* y, void* stream);
 /* The sampler's element-wise kernels exactly as svc_diffsvc_sample launches them (the parity tests; no copies, every
  * pointer a device pointer). x16 is the 16-bit copy for the next GEMM, rows of ld16 >= C halves of which columns

@@ -68,10 +68,22 @@ __device__ __forceinline__ half4v lds_tr16(const f16* p) {
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
-// BF: q / k / v and the output are bfloat16 (the bf16 operand variant, Op16<true>), P is rounded to bf16
-template <bool BF>
+__device__ __forceinline__ int att_len(int b, const int* lens) { return lens[b]; }
+
+// BF: q / k / v and the output are bfloat16 (the bf16 operand variant, Op16<true>), P is rounded to bf16.
+// RAGGED (a length table `lens` is given): utterance b has Lb = lens[b] (1..L) rows of its own; the batch row stride stays L. Every length the kernel
+// works with (tile count, query clamp, key-row clamp, tail mask) is then Lb, so the utterance sees the tiles, the
+// FIRST / TAIL peeling and the rescale ballots of a launch with L = Lb on that clip alone (bit-identical output), no
+// q / k / v row >= Lb is read (such rows may hold anything), and output rows Lb <= q < L are written as zeros.
+// The length table is a parameter pack, empty or one `const int*` (device int32 [B]): the non-ragged instances keep
+// the kernel's four-argument signature and compile to the code they had before the ragged form existed (Whisper's step
+// time rides on them; DESIGN.md "A8 for ragged batches" records the assembly comparison). Inlining a shared body into
+// two kernels did not: the same resources, but another register allocation and schedule.
+template <bool BF, typename... Lens>
 __global__ __launch_bounds__(256, 3) void attention_kernel(const f16* __restrict__ qkv, f16* __restrict__ out, int L,
-                                                           int D) {
+                                                           int D, Lens... lens) {
+  static_assert(sizeof...(Lens) <= 1, "attention_kernel: at most one length table");
+  constexpr bool RAGGED = sizeof...(Lens) == 1;
   using O = Op16<BF>;
   // double-buffered K / V^T tiles: tile kt + 1 is loaded into registers while tile kt is multiplied, then written to
   // the other buffer (one barrier per tile)
@@ -87,6 +99,21 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(const f16* __restrict
   const int qblk = wg % nq, h = (wg / nq) % H, b = wg / (nq * H);
   const int ld = 3 * D;
   const f16* base = qkv + (int64_t)b * L * ld;
+  const int Ls = L;  // the batch row stride
+  if constexpr (RAGGED) {
+    L = att_len(b, lens...);  // from here on L is this utterance's own length
+    // A query block at or past the utterance's end holds no query: its rows of this head are zeroed and the workgroup
+    // leaves. qblk, b and L derive from blockIdx and a table entry indexed by b alone, so all 256 threads take the
+    // same side of this branch (no partial exit), and it lies before the first __syncthreads().
+    if (qblk * ATT_QT >= L) {
+      const int nrow = min(ATT_QT, Ls - qblk * ATT_QT);
+      for (int i = tid; i < nrow * 8; i += 256) {  // 8 16-byte chunks per 64-column row
+        f16* orow = out + ((int64_t)b * Ls + qblk * ATT_QT + (i >> 3)) * D + h * 64;
+        *reinterpret_cast<u32x4*>(orow + (i & 7) * 8) = (u32x4){0u, 0u, 0u, 0u};
+      }
+      return;
+    }
+  }
   const int qw0 = qblk * ATT_QT + wave * 32;  // first query of this wave
   const int g = lane >> 4, c16 = lane & 15;
 
@@ -298,8 +325,15 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(const f16* __restrict
   for (int f = 0; f < 2; ++f) {
     const float inv = 1.0f / ol[f][0];
     const int q = qw0 + f * 16 + c16;
+    if constexpr (RAGGED) {
+      if (q >= L && q < Ls) {  // padding rows of a partly valid query block
+        f16* zrow = out + ((int64_t)b * Ls + q) * D + h * 64;
+#pragma unroll
+        for (int df = 0; df < 4; ++df) *reinterpret_cast<uint2*>(zrow + df * 16 + 4 * g) = make_uint2(0u, 0u);
+      }
+    }
     if (q >= L) continue;
-    f16* orow = out + ((int64_t)b * L + q) * D + h * 64;
+    f16* orow = out + ((int64_t)b * Ls + q) * D + h * 64;
 #pragma unroll
     for (int df = 0; df < 4; ++df) {
       union { uint2 u; f16 e[4]; } pk;
@@ -310,13 +344,18 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(const f16* __restrict
   }
 }
 
-int attention(const f16* qkv, f16* out, int B, int L, int D, hipStream_t s, bool bf16) {
+// lens (device int32 [B], each 1..L, or NULL): per-utterance lengths, see attention_kernel
+int attention(const f16* qkv, f16* out, int B, int L, int D, hipStream_t s, bool bf16, const int* lens) {
   SVC_REQUIRE(D % 64 == 0 && L > 0 && B > 0, "attention: bad shape B=%d L=%d D=%d", B, L, D);
   const int64_t nwg = (int64_t)((L + ATT_QT - 1) / ATT_QT) * (D / 64) * B;
   SVC_REQUIRE(nwg < (1ll << 31), "attention: grid");
   dim3 grid((unsigned)nwg);
   const int tok = prof_begin("attention", 4.0 * B * (double)L * L * D, 0.0, s);
-  if (bf16)
+  if (lens && bf16)
+    hipLaunchKernelGGL((attention_kernel<true, const int*>), grid, dim3(256), 0, s, qkv, out, L, D, lens);
+  else if (lens)
+    hipLaunchKernelGGL((attention_kernel<false, const int*>), grid, dim3(256), 0, s, qkv, out, L, D, lens);
+  else if (bf16)
     hipLaunchKernelGGL(attention_kernel<true>, grid, dim3(256), 0, s, qkv, out, L, D);
   else
     hipLaunchKernelGGL(attention_kernel<false>, grid, dim3(256), 0, s, qkv, out, L, D);

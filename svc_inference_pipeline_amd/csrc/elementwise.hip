@@ -311,6 +311,59 @@ int content_map_hubert(const float* src, int B, int src_rows, int ld_src, int T,
   return SVC_OK;
 }
 
+// Ragged batch (svc_map_content_ragged): utterance b maps its own src rows to its own Tb frames exactly as
+// content_map_kernel does for a batch of that shape (the same source rows, sum order and rounding), and its output
+// rows Tb <= jo < T are zeros. tab (device int32 [2B]): Tb [B] then n_down [B] (the mapped length; = Tb for the
+// Whisper rule). The host has checked that every source row read lies inside the utterance's own rows.
+__global__ void content_map_ragged_kernel(const float* __restrict__ src, int src_rows_per_utt, int ld_src,
+                                          f16* __restrict__ dst, int ld_dst, int T, int D, const int* __restrict__ tab,
+                                          bool bf) {
+  const int jo = blockIdx.x, b = blockIdx.y, B = gridDim.y;
+  const int Tb = tab[b];
+  f16* drow = dst + ((int64_t)b * T + jo) * ld_dst;
+  if (jo >= Tb) {  // (block-uniform)
+    for (int c = threadIdx.x; c < D; c += blockDim.x) drow[c] = (f16)0.0f;  // +0 in binary16 and in bfloat16
+    return;
+  }
+  const int j = min(jo, tab[B + b] - 1);
+  const float* sb = src + (int64_t)b * src_rows_per_utt * ld_src;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc += sb[(int64_t)((8 * j + i) / 15) * ld_src + c];
+    drow[c] = enc16_lo(acc / 8.0f, bf);
+  }
+}
+
+int content_map_ragged(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                       const int* tab, hipStream_t s, bool bf) {
+  hipLaunchKernelGGL(content_map_ragged_kernel, dim3(T, B), dim3(256), 0, s, src, src_rows, ld_src, dst, ld_dst, T, D,
+                     tab, bf);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
+// ragged batches: rows t >= Tb[b] of a 16-bit [B][T] tensor with rows of ld halves are set to zero (ld % 8 == 0 and
+// a 16-byte aligned base: one 16-byte store per thread). max_tail (host) = the longest tail, T - min Tb: the grid
+// covers that many rows per utterance, so only padding rows get threads (none: no launch).
+__global__ void zero_tail16_kernel(f16* __restrict__ x, int T, int ld, const int* __restrict__ Tb) {
+  const int b = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int t0 = Tb[b];
+  if (t0 >= T || i >= (int64_t)(T - t0) * (ld / 8)) return;
+  *reinterpret_cast<uint4*>(x + ((int64_t)b * T + t0) * ld + i * 8) = make_uint4(0u, 0u, 0u, 0u);
+}
+
+int zero_tail_rows16(f16* x, int B, int T, int ld, const int* Tb, int max_tail, hipStream_t s) {
+  SVC_REQUIRE(ld % 8 == 0 && ((uintptr_t)x & 15) == 0 && max_tail >= 0 && max_tail <= T,
+              "zero_tail_rows16: ld=%d max_tail=%d T=%d", ld, max_tail, T);
+  if (max_tail == 0) return SVC_OK;
+  hipLaunchKernelGGL(zero_tail16_kernel, dim3((unsigned)cdiv64((int64_t)max_tail * (ld / 8), 256), B), dim3(256), 0, s,
+                     x, T, ld, Tb);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
 // ============================================================================ bucketize
 // torch.bucketize(x, bins) with right=False = number of bins < x. f0 is float64 and the f32 bins are
 // widened exactly (torch promotes to f64); energy is compared in f32 (modules/encoder.py:70,115).

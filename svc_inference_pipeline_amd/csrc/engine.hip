@@ -75,7 +75,7 @@ void prof_end(int tok, hipStream_t s) {
 }
 
 // kernels in other translation units
-int attention(const f16* qkv, f16* out, int B, int L, int D, hipStream_t s, bool bf16);
+int attention(const f16* qkv, f16* out, int B, int L, int D, hipStream_t s, bool bf16, const int* lens = nullptr);
 int layernorm_f16(const float* x, const float* g, const float* b, f16* y, int rows, int D, int ldy, hipStream_t s,
                   bool bf);
 int layernorm_f32(const float* x, const float* g, const float* b, float* y, int rows, int D, int ldy, hipStream_t s);
@@ -128,9 +128,14 @@ int diff_head(const f16* s16, const f16* Wsp, const float* bsp, int Nsp, int Ksp
 int pitch_shift(double* f0, int B, int T, double target, hipStream_t s);
 int content_map_hubert(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
                        hipStream_t s, bool bf);
-int hubert_frames5(const float* wav, int B, int64_t n, f16* out, bool split, hipStream_t s, bool bf);
+int content_map_ragged(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                       const int* tab, hipStream_t s, bool bf);
+int zero_tail_rows16(f16* x, int B, int T, int ld, const int* Tb, int max_tail, hipStream_t s);
+int hubert_frames5(const float* wav, int B, int64_t n, f16* out, bool split, hipStream_t s, bool bf,
+                   const int64_t* nb = nullptr);
 int groupnorm_gelu(const float* x, int B, int T, int C, const float* gamma, const float* beta, double* part,
-                   int max_chunks, float2* ss, f16* y, bool split, hipStream_t s, bool bf);
+                   int max_chunks, float2* ss, f16* y, bool split, hipStream_t s, bool bf, const int* Tb = nullptr,
+                   int nck_max = 0);
 int layernorm_dual(const float* x, const float* g, const float* b, float* y32, f16* y16, int rows, int D, bool split,
                    hipStream_t s, bool bf);
 int pack_qkv(const float* q, const float* k, const float* v, f16* qkv, int64_t rows, int D, float scale, hipStream_t s);
@@ -2047,6 +2052,40 @@ svc_status svc_map_content_ex(svc_ctx* c, const float* feats, int B, int src_row
   return content_map_hubert(feats, B, src_rows, D, T, D, (f16*)out, ld_out, (hipStream_t)stream, c->bf16);
 }
 
+svc_status svc_map_content_ragged(svc_ctx* c, const float* feats, int B, int src_rows, const int32_t* utt_src_rows,
+                                  int T, const int32_t* frames, int D, int mode, void* out, int ld_out, void* stream) {
+  SVC_REQUIRE(c, "map_content_ragged: null context");
+  SVC_REQUIRE(feats && out && B > 0 && D > 0 && ld_out >= D && src_rows >= 1 && T >= 1,
+              "map_content_ragged: bad args (B=%d src_rows=%d T=%d D=%d ld_out=%d)", B, src_rows, T, D, ld_out);
+  SVC_REQUIRE(mode == 0 || mode == 1, "map_content_ragged: mode %d", mode);
+  if (!utt_src_rows && !frames) return svc_map_content_ex(c, feats, B, src_rows, T, D, mode, out, ld_out, stream);
+  // each utterance is checked as content_map / content_map_hubert check a batch of its shape, before any HIP call
+  std::vector<int> tab((size_t)2 * B);
+  for (int b = 0; b < B; ++b) {
+    const int sb = utt_src_rows ? utt_src_rows[b] : src_rows, tb = frames ? frames[b] : T;
+    SVC_REQUIRE(sb >= 1 && sb <= src_rows && tb >= 1 && tb <= T,
+                "map_content_ragged: utterance %d: %d of %d source rows, %d of %d frames", b, sb, src_rows, tb, T);
+    if (mode == 0) {
+      SVC_REQUIRE(tb <= 2812 && tb * 8 / 15 + 1 <= sb, "content_map: utterance %d: T=%d src_rows=%d", b, tb, sb);
+      tab[B + b] = tb;
+    } else {
+      const int n_down = (int)((int64_t)sb * 15 / 8);
+      SVC_REQUIRE(n_down >= 1 && std::abs(tb - n_down) <= 3,
+                  "content_map_hubert: utterance %d: %d content frames map to %d rows but T=%d (|diff| > 3; "
+                  "utils/hubert.py:114-120)", b, sb, n_down, tb);
+      tab[B + b] = n_down;
+    }
+    tab[b] = tb;
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_main, s);
+  void* dev = nullptr;
+  int st = c->lens_main.put(tab.data(), tab.size() * sizeof(int), s, &dev);
+  if (st) return st;
+  return content_map_ragged(feats, B, src_rows, D, T, D, (f16*)out, ld_out, (const int*)dev, s, c->bf16);
+}
+
 // ---------------------------------------------------------------------------- hubert / contentvec (A8)
 static int64_t hubert_len(int64_t n, int upto) {
   static const int k[7] = {10, 3, 3, 3, 3, 2, 2}, st[7] = {5, 2, 2, 2, 2, 2, 2};
@@ -2054,10 +2093,14 @@ static int64_t hubert_len(int64_t n, int upto) {
   return n;
 }
 
-svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, float* feats, void* stream) {
-  CTX_READY(c);
+// utt (host int64 [B], validated by the caller, or NULL): ragged batch. Three things look across time and take the
+// utterance's own length: the GroupNorm statistics (its own t1 rows and chunk partition), the positional conv (its
+// 16-bit input operand is zeroed from row F_b on, the zero padding the clip has alone) and the attention (keys and
+// queries stop at F_b). The valid convs make frame i < F_b depend on samples < n_b only and the GEMMs and LayerNorms
+// are row-wise, so they run over the padded batch unchanged; rows >= F_b of feats are zeroed at the end.
+static int hubert_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* utt, float* feats,
+                              hipStream_t s) {
   SVC_REQUIRE(c->has_hubert, "hubert weights not loaded");
-  hipStream_t s = (hipStream_t)stream;
   const int64_t F64 = hubert_len(n, 7);
   SVC_REQUIRE(B > 0 && F64 >= 1 && (int64_t)B * hubert_len(n, 1) < (1LL << 31), "hubert: B=%d n=%lld", B,
               (long long)n);
@@ -2075,6 +2118,29 @@ svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, f
                 (size_t)B * Cc * 8 + (size_t)B * (t[2] + t[3]) * Cc * 2 * X3 + rowsF * Cc * (4 + 2 * X3) +
                 rowsF * D * (4 + 2 * X3) + rowsF * 3 * D * 2 + rowsF * D * 2 + rowsF * Fd * 2 * X3 + 32 * 4096;
   int st;
+  // per-utterance tables: samples (int64 [B]), then conv_layers[0] rows t1 and frames F (int32 [B] each)
+  const int64_t* nb_dev = nullptr;
+  const int *t1_dev = nullptr, *F_dev = nullptr;
+  int nck_max = 0, F_min = F;
+  RingRetire retire_(c->lens_main, s);
+  if (utt) {
+    std::vector<char> buf((size_t)B * 16);
+    int64_t* nv = reinterpret_cast<int64_t*>(buf.data());
+    int* tv = reinterpret_cast<int*>(buf.data() + (size_t)B * 8);
+    for (int b = 0; b < B; ++b) {
+      nv[b] = utt[b];
+      tv[b] = (int)hubert_len(utt[b], 1);
+      tv[B + b] = (int)hubert_len(utt[b], 7);
+      F_min = std::min(F_min, tv[B + b]);
+      const int chunks = std::max(1, std::min(kChunks, cdiv(tv[b], 256)));
+      nck_max = std::max(nck_max, cdiv(tv[b], cdiv(tv[b], chunks)));
+    }
+    void* dev = nullptr;
+    if ((st = c->lens_main.put(buf.data(), buf.size(), s, &dev))) return st;
+    nb_dev = reinterpret_cast<const int64_t*>(dev);
+    t1_dev = reinterpret_cast<const int*>(reinterpret_cast<char*>(dev) + (size_t)B * 8);
+    F_dev = t1_dev + B;
+  }
   if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
   c->ws.reset();
   // ---- feature extractor (wav2vec2 ConvFeatureExtractionModel, mode "default")
@@ -2087,12 +2153,13 @@ svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, f
   WS_GET(f16, pb, (size_t)B * t[3] * Cc * X3);
   WS_GET(float, c6, rowsF * Cc);
   WS_GET(f16, ln16, rowsF * Cc * X3);
-  if ((st = hubert_frames5(wav16, B, n, f5, sp, s, c->bf16))) return st;
+  if ((st = hubert_frames5(wav16, B, n, f5, sp, s, c->bf16, nb_dev))) return st;
   EpiArgs e = epi();
   e.out32 = c0;
   e.ld32 = Cc;
   if ((st = run_gemm(c->hconv[0], f5, w5, w5, B, (int)R5, (int)t[1], e, s, "hubert.conv0"))) return st;
-  if ((st = groupnorm_gelu(c0, B, (int)t[1], Cc, c->hgn_g, c->hgn_b, part, kChunks, gss, g16, sp, s, c->bf16)))
+  if ((st = groupnorm_gelu(c0, B, (int)t[1], Cc, c->hgn_g, c->hgn_b, part, kChunks, gss, g16, sp, s, c->bf16, t1_dev,
+                           nck_max)))
     return st;
   const f16* in = g16;
   for (int i = 1; i < 7; ++i) {
@@ -2126,6 +2193,9 @@ svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, f
   // ---- TransformerEncoder: x += GELU(pos_conv(x)) per group, then LayerNorm (layer_norm_first = False)
   const int Cg = D / c->hPosG;
   if (sp && (st = f32_to_f16x3_grouped(x, x16, (int)rowsF, D, Cg, s, c->bf16))) return st;  // group g: [hi | lo | hi] x Cg
+  // ragged: pos_conv (k = 128, pad 64) reads up to 64 rows past an utterance's end, which alone are its zero padding.
+  // Only the padding rows of the operand are rewritten (the projection's f32 output x keeps them: row-wise from here)
+  if (F_dev && (st = zero_tail_rows16(x16, B, F, D * X3, F_dev, F - F_min, s))) return st;
   for (int gi = 0; gi < c->hPosG; ++gi) {
     e = epi();
     e.act = ACT_GELU;
@@ -2151,7 +2221,7 @@ svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, f
     e.scale_cols2 = D;
     e.col_scale2 = qk_scale * ATT_LOG2E;
     if ((st = run_gemm(b.qkv, x16, D * X3, D * X3, B, F, F, e, s, "hubert.qkv"))) return st;
-    if ((st = attention(qkv, o16, B, F, D, s, c->bf16))) return st;
+    if ((st = attention(qkv, o16, B, F, D, s, c->bf16, F_dev))) return st;
     e = epi();
     e.add_row = x;
     e.ld_add_row = D;
@@ -2176,7 +2246,27 @@ svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, f
   e = epi();
   e.out32 = feats;
   e.ld32 = c->hFinal;
-  return run_gemm(c->hfinal, x16, D * X3, D * X3, B, F, F, e, s, "hubert.final_proj");
+  if ((st = run_gemm(c->hfinal, x16, D * X3, D * X3, B, F, F, e, s, "hubert.final_proj"))) return st;
+  return F_dev ? zero_tail_rows(feats, B, F, c->hFinal, F_dev, s) : SVC_OK;
+}
+
+svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, float* feats, void* stream) {
+  CTX_READY(c);
+  return hubert_encode_impl(c, wav16, B, n, nullptr, feats, (hipStream_t)stream);
+}
+
+svc_status svc_hubert_encode_ragged(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* utt_samples,
+                                    float* feats, void* stream) {
+  // the arguments and the length table are checked before the context is touched (no HIP call)
+  SVC_REQUIRE(c, "hubert_encode_ragged: null context");
+  SVC_REQUIRE(wav16 && feats, "hubert_encode_ragged: null %s", wav16 ? "feats" : "wav16k");
+  SVC_REQUIRE(B > 0, "hubert_encode_ragged: B=%d", B);
+  for (int b = 0; utt_samples && b < B; ++b)
+    SVC_REQUIRE(utt_samples[b] >= 400 && utt_samples[b] <= n,
+                "hubert_encode_ragged: utterance %d: %lld samples (at least 400 for one frame, batch length %lld)", b,
+                (long long)utt_samples[b], (long long)n);
+  CTX_READY(c);
+  return hubert_encode_impl(c, wav16, B, n, utt_samples, feats, (hipStream_t)stream);
 }
 
 int64_t svc_hubert_frames(int64_t n_samples) { return hubert_len(n_samples, 7); }
@@ -3092,6 +3182,33 @@ svc_status svc_op_attention(const float* q, const float* k, const float* v, int 
   WS_GET(f16, o16, rows * D);
   if ((st = pack_qkv(q, k, v, qkv, (int64_t)rows, D, powf(64.0f, -0.25f), s))) return st;
   if ((st = attention(qkv, o16, B, L, D, s, false))) return st;
+  return f16_to_f32(o16, out, (int64_t)rows * D, s);
+}
+
+svc_status svc_op_attention_ragged(const float* q, const float* k, const float* v, int B, int L, int D,
+                                   const int32_t* lens, float* out, void* stream) {
+  SVC_REQUIRE(q && k && v && out, "op_attention_ragged: null tensor");
+  SVC_REQUIRE(D > 0 && D % 64 == 0 && L > 0 && B > 0, "op_attention_ragged: bad shape B=%d L=%d D=%d", B, L, D);
+  for (int b = 0; lens && b < B; ++b)
+    SVC_REQUIRE(lens[b] >= 1 && lens[b] <= L, "op_attention_ragged: utterance %d: length %d outside 1..%d", b, lens[b],
+                L);
+  if (!lens) return svc_op_attention(q, k, v, B, L, D, out, stream);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  int st;
+  const size_t rows = (size_t)B * L;
+  if ((st = c->ws.reserve(std::max(rows * D * 2 * 4 + 4096, c->ws.cap)))) return st;
+  c->ws.reset();
+  WS_GET(f16, qkv, rows * 3 * D);
+  WS_GET(f16, o16, rows * D);
+  RingRetire retire_(c->lens_main, s);
+  void* dev = nullptr;
+  if ((st = c->lens_main.put(lens, (size_t)B * sizeof(int32_t), s, &dev))) return st;
+  // (the padding rows are packed too: element-wise, whatever they hold)
+  if ((st = pack_qkv(q, k, v, qkv, (int64_t)rows, D, powf(64.0f, -0.25f), s))) return st;
+  if ((st = attention(qkv, o16, B, L, D, s, false, (const int*)dev))) return st;
   return f16_to_f32(o16, out, (int64_t)rows * D, s);
 }
 

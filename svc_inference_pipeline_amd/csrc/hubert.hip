@@ -8,6 +8,9 @@
 //                   partials per row chunk (coalesced: a block streams whole rows, each lane owns 2 channels).
 //   gn_finalize   : partials -> per (utterance, channel) scale = gamma * rstd, shift = beta - mean * scale.
 //   gn_gelu_apply : y16 = GELU(x * scale + shift), f32 -> f16, 16-byte vectors.
+//   Ragged batches (svc_hubert_encode_ragged): frames5 reads samples at or past an utterance's own count as zero, and
+//   colstats / gn_finalize take per-utterance row counts and partition each utterance's rows as groupnorm_gelu would
+//   for a batch of that length alone, so its f64 partials add in the same order and scale / shift are bit-identical.
 //   layernorm_dual: LayerNorm writing both the f32 residual stream and its f16 GEMM operand (post-LN layers).
 #include "common.h"
 
@@ -15,11 +18,13 @@ namespace svc {
 
 // SPLIT: 16 halves per row = [hi(5) | lo(5) | hi(5) | 0] (split-fp16 operand of the split-packed conv_layers[0])
 template <bool SPLIT>
-__global__ void frames5_kernel(const float* __restrict__ wav, int64_t n, int64_t rows, f16* __restrict__ out, bool bf) {
+__global__ void frames5_kernel(const float* __restrict__ wav, int64_t n, int64_t rows, f16* __restrict__ out, bool bf,
+                               const int64_t* __restrict__ nb) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one output row (8 or 16 halves)
   const int b = blockIdx.y;
   if (i >= rows) return;
   const float* w = wav + (int64_t)b * n;
+  const int64_t nv = nb ? nb[b] : n;  // the utterance's own samples: the row's padding is never read
   constexpr int W = SPLIT ? 16 : 8;
   union { uint4 u[W / 8]; f16 h[W]; } pk;
 #pragma unroll
@@ -27,7 +32,7 @@ __global__ void frames5_kernel(const float* __restrict__ wav, int64_t n, int64_t
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
     const int64_t k = 5 * i + j;
-    const float v = k < n ? w[k] : 0.0f;
+    const float v = k < nv ? w[k] : 0.0f;
     const f16 hi = enc16_lo(v, bf);
     pk.h[j] = hi;
     if constexpr (SPLIT) {
@@ -39,21 +44,37 @@ __global__ void frames5_kernel(const float* __restrict__ wav, int64_t n, int64_t
   for (int q = 0; q < W / 8; ++q) *reinterpret_cast<uint4*>(out + ((int64_t)b * rows + i) * W + q * 8) = pk.u[q];
 }
 
-int hubert_frames5(const float* wav, int B, int64_t n, f16* out, bool split, hipStream_t s, bool bf) {
+// nb (device int64 [B] or NULL): per-utterance sample counts (<= n)
+int hubert_frames5(const float* wav, int B, int64_t n, f16* out, bool split, hipStream_t s, bool bf,
+                   const int64_t* nb) {
   const int64_t rows = cdiv64(n, 5);
   if (split)
-    hipLaunchKernelGGL(frames5_kernel<true>, dim3(cdiv(rows, 256), B), dim3(256), 0, s, wav, n, rows, out, bf);
+    hipLaunchKernelGGL(frames5_kernel<true>, dim3(cdiv(rows, 256), B), dim3(256), 0, s, wav, n, rows, out, bf, nb);
   else
-    hipLaunchKernelGGL(frames5_kernel<false>, dim3(cdiv(rows, 256), B), dim3(256), 0, s, wav, n, rows, out, bf);
+    hipLaunchKernelGGL(frames5_kernel<false>, dim3(cdiv(rows, 256), B), dim3(256), 0, s, wav, n, rows, out, bf, nb);
   SVC_LAUNCH_CHECK();
   return SVC_OK;
 }
 
-// grid (chunks, B), 256 threads; lane pair p = 2 adjacent channels
+// the row partition of groupnorm_gelu for T rows: chunk rows per block, the number of blocks as return value
+__host__ __device__ __forceinline__ int gn_partition(int T, int max_chunks, int* chunk) {
+  const int chunks = max(1, min(max_chunks, (T + 255) / 256));
+  *chunk = (T + chunks - 1) / chunks;
+  return (T + *chunk - 1) / *chunk;
+}
+
+// grid (chunks, B), 256 threads; lane pair p = 2 adjacent channels. Tb (or NULL): utterance b has Tb[b] <= T rows and
+// its own partition of them (blocks past its last chunk write nothing); the partials keep the grid's stride.
 __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__ x, int T, int C, int chunk,
-                                                       double* __restrict__ part) {
+                                                       double* __restrict__ part, const int* __restrict__ Tb,
+                                                       int max_chunks) {
   const int ck = blockIdx.x, b = blockIdx.y, nck = gridDim.x;
-  const int r0 = ck * chunk, r1 = min(T, r0 + chunk);
+  int Tv = T;
+  if (Tb) {
+    Tv = Tb[b];
+    if (ck >= gn_partition(Tv, max_chunks, &chunk)) return;
+  }
+  const int r0 = ck * chunk, r1 = min(Tv, r0 + chunk);
   const float* xb = x + (int64_t)b * T * C;
   for (int p = threadIdx.x; p < C / 2; p += blockDim.x) {
     double s0 = 0, s1 = 0, q0 = 0, q1 = 0;
@@ -78,12 +99,20 @@ __global__ __launch_bounds__(256) void colstats_kernel(const float* __restrict__
   }
 }
 
+// Tb (or NULL): utterance b's statistics are over its own Tb[b] rows, held in the first chunks of its own partition
 __global__ void gn_finalize_kernel(const double* __restrict__ part, int nck, int T, int C, const float* __restrict__ g,
-                                   const float* __restrict__ be, float eps, float2* __restrict__ ss) {
+                                   const float* __restrict__ be, float eps, float2* __restrict__ ss,
+                                   const int* __restrict__ Tb, int max_chunks) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
   if (c >= C) return;
+  int nown = nck;
+  if (Tb) {
+    int chunk;
+    T = Tb[b];
+    nown = gn_partition(T, max_chunks, &chunk);
+  }
   double s = 0, q = 0;
-  for (int k = 0; k < nck; ++k) {
+  for (int k = 0; k < nown; ++k) {
     const double* p = part + (((int64_t)b * nck + k) * C + c) * 2;
     s += p[0];
     q += p[1];
@@ -126,17 +155,20 @@ __global__ void gn_gelu_apply_kernel(const float* __restrict__ x, const float2* 
 }
 
 // Fp32GroupNorm(C, C) + GELU over x f32 [B][T][C] -> y f16 [B][T][C]. part: >= B * chunks * C * 2 doubles,
-// ss: B * C float2.
+// ss: B * C float2. Tb (device int32 [B], each 1..T, or NULL) with nck_max = the largest block count of any
+// utterance's own partition (host-computed): ragged batch, statistics over each utterance's own rows; every row of
+// the batch is still normalised (rows past an utterance's end feed nothing that is kept).
 int groupnorm_gelu(const float* x, int B, int T, int C, const float* gamma, const float* beta, double* part,
-                   int max_chunks, float2* ss, f16* y, bool split, hipStream_t s, bool bf) {
+                   int max_chunks, float2* ss, f16* y, bool split, hipStream_t s, bool bf, const int* Tb, int nck_max) {
   SVC_REQUIRE(C % 8 == 0 && T > 0 && B > 0, "groupnorm: B=%d T=%d C=%d", B, T, C);
-  const int chunks = std::max(1, std::min(max_chunks, cdiv(T, 256)));
-  const int chunk = cdiv(T, chunks);
-  const int nck = cdiv(T, chunk);
+  int chunk;
+  int nck = gn_partition(T, max_chunks, &chunk);
+  if (Tb) nck = nck_max;
+  SVC_REQUIRE(nck >= 1 && nck <= max_chunks, "groupnorm: %d chunks of at most %d", nck, max_chunks);
   const int tok = prof_begin("groupnorm_gelu", 0.0, (double)B * T * C * (4 + 4 + 2), s);
-  hipLaunchKernelGGL(colstats_kernel, dim3(nck, B), dim3(256), 0, s, x, T, C, chunk, part);
+  hipLaunchKernelGGL(colstats_kernel, dim3(nck, B), dim3(256), 0, s, x, T, C, chunk, part, Tb, max_chunks);
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(C, 256), B), dim3(256), 0, s, part, nck, T, C, gamma, beta, 1e-5f,
-                     ss);
+                     ss, Tb, max_chunks);
   const int64_t nvec = (int64_t)B * T * C / 8;
   if (split)
     hipLaunchKernelGGL(gn_gelu_apply_kernel<true>, dim3((unsigned)cdiv64(nvec, 256)), dim3(256), 0, s, x, ss, y,

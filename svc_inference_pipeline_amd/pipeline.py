@@ -44,8 +44,14 @@ class ConvertResult:
 
 
 class SVCPipeline:
-    def __init__(self, engine: SVCEngine, f0_side=True, f0_method="parselmouth"):
-        """f0_side: run the 24 kHz features (mel / energy, F0, pitch shift) on the context's sub-stream 2 beside the
+    def __init__(self, engine: SVCEngine, f0_side=True, f0_method="parselmouth", hubert_ragged=None):
+        """hubert_ragged: a ragged batch's HuBERT / ContentVec features come from ONE padded encoder pass with
+        per-utterance lengths (svc_hubert_encode_ragged) and one ragged mapping launch; False: one encoder pass, one
+        mapping and one copy per exact-length bucket (the same values bit for bit; DESIGN.md "A8 for ragged batches").
+        None (default): the one-pass form with every engine that has the length-taking entry points (SVCEngine does:
+        its `ragged_hubert` is True), the per-bucket form with an engine object that lacks them. True with such an
+        engine is a ValueError, never a quiet fall-back. The form in use is `self.hubert_ragged`.
+        f0_side: run the 24 kHz features (mel / energy, F0, pitch shift) on the context's sub-stream 2 beside the
         content encoder (default; measured +0.4 %) instead of on the caller's stream.
         f0_method: "parselmouth" (utils/f0.py:120-161, what utils/acoustic_feature_extraction.py:53 uses) or "pyin"
         (utils/f0.py:95-117 get_f0_features_using_pyin, svc_f0_pyin; its 1 + N // hop frames cut to the mel frames)."""
@@ -54,6 +60,11 @@ class SVCPipeline:
         self.engine = engine
         self.f0_side = f0_side
         self.f0_method = f0_method
+        able = bool(getattr(engine, "ragged_hubert", False))
+        if hubert_ragged and not able:
+            raise ValueError("hubert_ragged=True: the engine has no hubert_encode(n_samples=) / map_content(frames=, "
+                             "src_rows=) (its ragged_hubert is not set)")
+        self.hubert_ragged = able if hubert_ragged is None else bool(hubert_ragged)
 
     def extract_f0(self, wav24, T, n_samples=None, T_b=None):
         """F0 by the configured method -> f64 [B, T] (rows past an utterance's T_b frames 0)."""
@@ -208,8 +219,9 @@ class SVCPipeline:
         """Content features for a ragged batch -> f16 [B, T, D]; rows [b, :T_b[b]] equal convert()'s for that clip
         alone. Whisper runs on zero-padded 16 kHz audio (pad_or_trim pads with zeros, so the padding is exact), in two
         groups: clips the reference maps in one 30 s window (T_b <= 2812) and long clips (per-window, see
-        whisper_content). HuBERT / ContentVec attends over every frame and normalises over time, so it runs per
-        exact-length bucket."""
+        whisper_content). HuBERT / ContentVec attends over every frame and normalises over time, so it takes the
+        lengths: one padded encoder pass and one mapping launch straight into its columns of the result
+        (hubert_ragged=False: one pass per exact-length bucket)."""
         e = self.engine
         m = e.cfg.mapper
         types = sorted(m.content_feature)
@@ -230,6 +242,13 @@ class SVCPipeline:
                         out[i, :T_b[i], col:col + w] = c[j, :T_b[i]]
             elif t in HUBERT_CONTENT_TYPES:
                 src = wavs16 if wavs16_float is None else wavs16_float
+                if self.hubert_ragged:
+                    w16, n16 = self._pad_stack(src)
+                    feats = e.hubert_encode(w16, n_samples=n16)
+                    e.map_content(feats, T, rule="hubert", out=out[:, :, col:col + w], frames=T_b,
+                                  src_rows=[e.hubert_frames(k) for k in n16])
+                    col += w
+                    continue
                 buckets = {}
                 for i in range(B):
                     buckets.setdefault((int(src[i].shape[-1]), T_b[i]), []).append(i)

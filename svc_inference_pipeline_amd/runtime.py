@@ -101,6 +101,8 @@ class SVCEngine:
     (e.g. {"content.wsplit_mlp": 0xffffff} to weight-split the MLP linears of all 24 Whisper blocks; an unknown key
     raises)."""
 
+    ragged_hubert = True  # hubert_encode takes n_samples, map_content takes frames / src_rows (SVCPipeline)
+
     def __init__(self, cfg, device=0, whisper_state=None, mapper_state=None, vocoder_state=None, hubert_state=None,
                  hubert_output_layer=9, content_split=2, head_split=True, config=None, operands="fp16"):
         check_supported(cfg)
@@ -246,29 +248,47 @@ class SVCEngine:
         _lib.call("svc_whisper_encode", self._ctx, _ptr(wav16), B, N, _ptr(feats), _stream())
         return feats
 
-    def map_content(self, feats, T, rule="whisper", out=None):
+    def map_content(self, feats, T, rule="whisper", out=None, frames=None, src_rows=None):
         """15:8 repeat/average to mel frames -> [B, T, D] in content_dtype (f16; bf16 with operands="bf16").
         rule "whisper": utils/whisper.py:31-81 (T <= 2812); rule "hubert": utils/hubert.py:83-134 (no cap, <= 3
         missing frames repeat the last one, more is an error). `out` may be a column slice [B, T, D] of a wider
-        buffer (concatenated content types)."""
+        buffer (concatenated content types).
+        frames / src_rows (ragged batch, host ints [B]): utterance b maps its first src_rows[b] rows of feats to
+        frames[b] frames as a batch of that shape would; its rows past frames[b] come back as zeros."""
         B, S, D = feats.shape
         if out is None:
             out = torch.empty(B, T, D, device=feats.device, dtype=self.content_dtype)
         assert out.shape == (B, T, D) and out.stride(2) == 1 and out.stride(0) == T * out.stride(1)
         assert out.dtype == self.content_dtype, f"map_content: out must be {self.content_dtype}"
         mode = {"whisper": 0, "hubert": 1}[rule]
+        if frames is not None or src_rows is not None:
+            _lib.call("svc_map_content_ragged", self._ctx, _ptr(feats.contiguous()), B, S,
+                      _host_lengths(src_rows, B, ctypes.c_int32), T, _host_lengths(frames, B, ctypes.c_int32), D, mode,
+                      ctypes.c_void_p(out.data_ptr()), out.stride(1), _stream())
+            return out
         _lib.call("svc_map_content_ex", self._ctx, _ptr(feats.contiguous()), B, S, T, D, mode,
                   ctypes.c_void_p(out.data_ptr()), out.stride(1), _stream())
         return out
 
-    def hubert_encode(self, wav16):
+    def hubert_frames(self, n_samples):
+        """frames of the conv feature extractor for a clip of n_samples 16 kHz samples"""
+        return int(_lib.load().svc_hubert_frames(int(n_samples)))
+
+    def hubert_encode(self, wav16, n_samples=None):
         """get_hubert_content (utils/hubert.py:31-47): wav16 f32 [B, N] (16 kHz float audio) -> ContentVec
-        features f32 [B, frames, final_dim] (time-major; the reference returns the transpose)."""
+        features f32 [B, frames, final_dim] (time-major; the reference returns the transpose).
+        n_samples (ragged batch, host ints [B], 400 <= n_b <= N): utterance b is wav16[b, :n_samples[b]] (the rest of
+        its row is not read); its hubert_frames(n_samples[b]) rows equal encoding that clip alone bit for bit, and its
+        rows past them come back as zeros."""
         B, N = wav16.shape
         fd, _ = ctypes.c_int(), ctypes.c_int()
         _lib.call("svc_hubert_dims", self._ctx, ctypes.byref(fd), None)
         F = int(_lib.load().svc_hubert_frames(N))
         feats = torch.empty(B, F, fd.value, device=wav16.device, dtype=torch.float32)
+        if n_samples is not None:
+            _lib.call("svc_hubert_encode_ragged", self._ctx, _ptr(wav16.contiguous()), B, N,
+                      _host_lengths(n_samples, B, ctypes.c_int64), _ptr(feats), _stream())
+            return feats
         _lib.call("svc_hubert_encode", self._ctx, _ptr(wav16.contiguous()), B, N, _ptr(feats), _stream())
         return feats
 
