@@ -9,6 +9,8 @@
  *   svc_pitch_shift     <- utils/acoustic_feature_extraction.py:48-52 pitch_shift
  *   svc_whisper_encode  <- utils/whisper.py:13-28 whisper_encoder (log_mel_spectrogram + AudioEncoder)
  *   svc_map_content     <- utils/whisper.py:31-81 get_mapped_whisper_features
+ *   svc_whisper_content_ragged <- utils/whisper.py:13-81, both of the above for a ragged batch: every 30 s window that
+ *                          exists encoded once in one pass, one mapping launch (svc_whisper_windows: a clip's windows)
  *   svc_hubert_encode   <- utils/hubert.py:31-47 get_hubert_content (svc_hubert_encode_ragged: a ragged batch in one pass)
  *   svc_map_content_ragged <- utils/hubert.py:83-134 get_mapped_features / utils/whisper.py:31-81, per utterance
  *   svc_condition       <- modules/encoder.py:165-201 EncoderFramework.forward
@@ -39,8 +41,12 @@
  *     stages, frames (int32 [B], mel frames) for the sampler and the vocoder; NULL means every utterance has the
  *     batch length. Each utterance is then computed exactly as a clip of its own length (its own reflect / zero /
  *     replicate padding, STFT frames, Praat frame grid, fade-out): outputs are bit-identical to converting it alone,
- *     and the rows past its end are written as zeros. Whisper needs no lengths: pad its 16 kHz input with zeros (as
- *     pad_or_trim does). HuBERT / ContentVec does need them (its GroupNorm normalises over time, its positional
+ *     and the rows past its end are written as zeros. svc_whisper_encode needs no lengths: pad its 16 kHz input with
+ *     zeros (as pad_or_trim does). A ragged Whisper batch as a whole goes through svc_whisper_content_ragged, which
+ *     takes utt_samples (int64 [B], 16 kHz samples) and frames (int32 [B], mel frames): clips of one 30 s window and
+ *     clips of several windows share ONE encoder pass over exactly the windows that exist, each window framed in place
+ *     from the padded batch (samples past an utterance's own count are never read), and one mapping launch writes
+ *     every utterance's frames. HuBERT / ContentVec needs lengths too (its GroupNorm normalises over time, its positional
  *     convolution reads past the end and its attention looks at every key): svc_hubert_encode_ragged takes
  *     utt_samples (int64 [B], 16 kHz samples) and svc_map_content_ragged takes each utterance's source rows and mel
  *     frames (int32 [B] each), so a ragged ContentVec batch is one encoder pass and one mapping launch. The tables
@@ -146,6 +152,31 @@ svc_status svc_map_content_ex(svc_ctx* ctx, const float* feats, int B, int src_r
 svc_status svc_map_content_ragged(svc_ctx* ctx, const float* feats, int B, int src_rows, const int32_t* utt_src_rows,
                                   int T, const int32_t* frames, int D, int mode, void* out_f16, int ld_out,
                                   void* stream);
+
+/* host-only: Whisper windows of a clip of `frames` mel frames: 1 for 1..2812 (the reference's single 30 s window,
+   utils/whisper.py:52-56), else ceil(frames / 2805) windows of 478 720 samples (29.92 s = 1496 encoder rows =
+   2805 mel frames); -1 for frames < 1 */
+int svc_whisper_windows(int frames);
+
+/* A5+A6+A7 for a ragged batch: wav16 f32 [B][n_samples] (int16-quantised 16 kHz), utterance b = its first
+   utt_samples[b] samples -> out16 [B*T] rows of ld_out halves (columns 0..D-1; f16, or bf16 with operands.bf16).
+   Utterance b has W_b = svc_whisper_windows(frames[b]) windows. A single window reads samples [0, min(utt_samples[b],
+   480000)); window w of a longer clip reads [w * 478720, w * 478720 + clamp(utt_samples[b] - w * 478720, 0, 478720));
+   the rest of each window's 30 s is zeros (pad_or_trim), a window may hold no samples at all, and samples at or past
+   utt_samples[b] are never read. All W = sum W_b windows go through the encoder in ONE pass (log-mel with its
+   per-window maximum, conv stem, blocks, ln_post; tune.whisper_streams sub-batches split over windows). One launch
+   then maps: row t < frames[b] comes from window (W_b == 1 ? 0 : t / 2805), local row t' = t - 2805 * window, by
+   svc_map_content's rule (source rows (8 t' + i) / 15, i = 0..7, summed in that order in f32, / 8); rows frames[b] ..
+   T-1 are +0 in columns 0..D-1; columns at or past D of a wider buffer are not touched. Every utterance equals
+   svc_whisper_encode + svc_map_content on its own windows bit for bit.
+   feats_out: optional device f32 [W][n_ctx][n_state], the encoder output of every window, utterance-major (NULL: it
+   stays in the workspace, which is sized for W windows as svc_whisper_encode sizes it for B).
+   utt_samples: HOST int64 [B], each 0..n_samples, NULL = n_samples; frames: HOST int32 [B], each 1..T, NULL = T. Both
+   are checked before any HIP call: a bad entry is SVC_ERR_INVALID naming the utterance, as are a null pointer, B < 1,
+   ld_out < D, missing Whisper weights and a row count beyond int. The window table goes through the main length ring. */
+svc_status svc_whisper_content_ragged(svc_ctx* ctx, const float* wav16, int B, int64_t n_samples,
+                                      const int64_t* utt_samples, int T, const int32_t* frames,
+                                      void* out16, int ld_out, float* feats_out, void* stream);
 
 /* A8 (variant): HuBERT/ContentVec content encoder, replacing utils/hubert.py:31-47 get_hubert_content
    (fairseq HubertModel.extract_features(output_layer = config "hubert.output_layer", default 9) + final_proj).

@@ -35,6 +35,9 @@ PROTOTYPES = {
     "svc_hubert_encode_ragged": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
     "svc_map_content_ragged": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                        c_void_p, c_int, c_void_p]),
+    "svc_whisper_windows": (c_int, [c_int]),
+    "svc_whisper_content_ragged": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_void_p, c_void_p]),
     "svc_hubert_frames": (c_int64, [c_int64]),
     "svc_hubert_dims": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "svc_condition": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -343,6 +343,47 @@ int content_map_ragged(const float* src, int B, int src_rows, int ld_src, int T,
   return SVC_OK;
 }
 
+// Ragged Whisper batch (svc_whisper_content_ragged): src holds the encoder output of every window of every utterance,
+// utterance-major, win_rows (n_ctx) rows each. tab (device int32 [2B]): per utterance its first window and its Tb
+// frames. A clip of Tb <= 2812 frames has the reference's single window; a longer one has windows of 2805 frames each
+// (1496 source rows), and output row jo comes from window jo / 2805, local row jo % 2805, by content_map_kernel's
+// arithmetic: the 8 taps (8 t' + i) / 15 are non-decreasing and span at most two source rows, so each is loaded once
+// and the eight additions keep their order (the same values added in the same sequence: the same bits). Output rows
+// Tb <= jo < T are zeros. Every branch is on block-uniform quantities.
+__global__ void content_map_windows_kernel(const float* __restrict__ src, int win_rows, int ld_src,
+                                           f16* __restrict__ dst, int ld_dst, int T, int D, const int* __restrict__ tab,
+                                           bool bf) {
+  const int jo = blockIdx.x, b = blockIdx.y;
+  const int w0 = tab[2 * b], Tb = tab[2 * b + 1];
+  f16* drow = dst + ((int64_t)b * T + jo) * ld_dst;
+  if (jo >= Tb) {
+    for (int c = threadIdx.x; c < D; c += blockDim.x) drow[c] = (f16)0.0f;  // +0 in binary16 and in bfloat16
+    return;
+  }
+  const int w = Tb <= 2812 ? 0 : jo / 2805;
+  const int j = jo - 2805 * w;
+  const int r0 = (8 * j) / 15, r1 = (8 * j + 7) / 15;
+  const int n0 = min(8, 15 * (r0 + 1) - 8 * j);  // taps that fall on r0: those with 8 j + i < 15 (r0 + 1)
+  const float* s0 = src + ((int64_t)(w0 + w) * win_rows + r0) * ld_src;
+  const float* s1 = src + ((int64_t)(w0 + w) * win_rows + r1) * ld_src;
+  for (int c = threadIdx.x; c < D; c += blockDim.x) {
+    const float a0 = s0[c], a1 = s1[c];
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc += i < n0 ? a0 : a1;
+    drow[c] = enc16_lo(acc / 8.0f, bf);
+  }
+}
+
+int content_map_windows(const float* src, int B, int win_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                        const int* tab, hipStream_t s, bool bf) {
+  SVC_REQUIRE(win_rows >= 1500, "content_map_windows: %d rows per window (1500: utils/whisper.py:56)", win_rows);
+  hipLaunchKernelGGL(content_map_windows_kernel, dim3(T, B), dim3(256), 0, s, src, win_rows, ld_src, dst, ld_dst, T, D,
+                     tab, bf);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
 // ragged batches: rows t >= Tb[b] of a 16-bit [B][T] tensor with rows of ld halves are set to zero (ld % 8 == 0 and
 // a 16-byte aligned base: one 16-byte store per thread). max_tail (host) = the longest tail, T - min Tb: the grid
 // covers that many rows per utterance, so only padding rows get threads (none: no launch).

@@ -130,6 +130,8 @@ int content_map_hubert(const float* src, int B, int src_rows, int ld_src, int T,
                        hipStream_t s, bool bf);
 int content_map_ragged(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
                        const int* tab, hipStream_t s, bool bf);
+int content_map_windows(const float* src, int B, int win_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                        const int* tab, hipStream_t s, bool bf);
 int zero_tail_rows16(f16* x, int B, int T, int ld, const int* Tb, int max_tail, hipStream_t s);
 int hubert_frames5(const float* wav, int B, int64_t n, f16* out, bool split, hipStream_t s, bool bf,
                    const int64_t* nb = nullptr);
@@ -1903,14 +1905,22 @@ svc_status svc_pitch_shift(svc_ctx* c, double* f0, int B, int T, double target_m
 }
 
 // ---------------------------------------------------------------------------- whisper
-svc_status svc_whisper_encode(svc_ctx* c, const float* wav16, int B, int64_t n, float* feats, void* stream) {
-  CTX_READY(c);
+static const int64_t kWhisperSamples = 480000;  // utils/whisper_extractor/audio.py:18 (30 s @ 16 kHz)
+static const int64_t kWhisperWindow = 478720;   // samples per window of a long clip: 29.92 s = 1496 encoder rows
+static const int kWindowFrames = 2805;          // = 1496 * 15 / 8 mel frames, so every window starts on a mel frame
+static const int kMaxMapped = 2812;             // utils/whisper.py:56 (1500 * 15 // 8): the single 30 s window's frames
+
+// The encoder over B 30 s windows. rows (device int64 [B][2], or NULL): window b holds rows[2b + 1] samples starting at
+// wav16 + rows[2b] (DftArgs::rows), zeros after them; NULL is the uniform batch, window b = wav16[b][0 .. min(n, 30 s)).
+// feats f32 [B][n_ctx][n_state], or NULL: taken from the workspace; *feats_used receives the buffer either way.
+static int whisper_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* rows, float* feats,
+                               float** feats_used, hipStream_t s) {
   SVC_REQUIRE(c->has_whisper, "whisper weights not loaded");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t NS = 480000;  // utils/whisper_extractor/audio.py:18 (30 s @ 16 kHz)
+  const int64_t NS = kWhisperSamples;
   const int F = 3000, D = c->wD, L = c->wctx;
-  SVC_REQUIRE(B > 0 && n > 0, "whisper: B=%d n=%lld", B, (long long)n);
+  SVC_REQUIRE(B > 0 && (rows || n > 0), "whisper: B=%d n=%lld", B, (long long)n);
   SVC_REQUIRE(L * 2 == F, "whisper: n_ctx %d != 1500", L);
+  SVC_REQUIRE((int64_t)B * F < (1LL << 31), "whisper: %d windows of %d rows overflow the row count", B, F);
   const int nb = 201;
   const size_t rows1 = (size_t)B * F, rows2 = (size_t)B * L;
   const int X3 = c->content_split ? 3 : 1;  // split-fp16 block operands are [hi | lo | hi] rows
@@ -1918,9 +1928,15 @@ svc_status svc_whisper_encode(svc_ctx* c, const float* wav16, int B, int64_t n, 
   const int LDM = XS == 3 ? c->wstem_ld : c->wmels;  // the stem operand's row stride
   size_t need = rows1 * c->wmels * 4 + rows1 * LDM * 2 + rows1 * D * 2 * XS /*h1*/ +
                 rows2 * D * 4 + rows2 * D * 2 * X3 + rows2 * 3 * D * 2 + rows2 * D * 2 + rows2 * 4 * D * 2 * X3 + 64 * 4096;
+  if (!feats) need += rows2 * D * 4 + 4096;
   int st;
   if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
   c->ws.reset();
+  if (!feats) {
+    WS_GET(float, fws, rows2 * D);
+    feats = fws;
+  }
+  if (feats_used) *feats_used = feats;
   WS_GET(float, ls, rows1 * c->wmels);
   WS_GET(f16, lm16, rows1 * LDM);
   WS_GET(float, mx, B);
@@ -1929,6 +1945,7 @@ svc_status svc_whisper_encode(svc_ctx* c, const float* wav16, int B, int64_t n, 
   a.wav_stride = n;
   a.n_valid = std::min<int64_t>(n, NS);
   a.n_logical = NS;
+  a.rows = rows;
   a.n_fft = 400;
   a.hop = 160;
   a.pad = 200;
@@ -2035,6 +2052,76 @@ svc_status svc_whisper_encode(svc_ctx* c, const float* wav16, int B, int64_t n, 
     }
   }
   return layernorm_f32(x, c->wlnp_g, c->wlnp_b, feats, (int)rows2, D, D, s);
+}
+
+svc_status svc_whisper_encode(svc_ctx* c, const float* wav16, int B, int64_t n, float* feats, void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(feats, "whisper: null feats");
+  return whisper_encode_impl(c, wav16, B, n, nullptr, feats, nullptr, (hipStream_t)stream);
+}
+
+int svc_whisper_windows(int frames) {
+  if (frames < 1) return -1;
+  return frames <= kMaxMapped ? 1 : (frames - 1) / kWindowFrames + 1;
+}
+
+// A ragged Whisper batch: every window that exists goes through the encoder once, in one pass, framed in place from
+// the padded batch through the per-window table; one mapping launch writes each utterance's frames from its own
+// windows. Table in the main length ring: int64 [W][2] (source offset, valid samples), then int32 [B][2] (first
+// window, frames).
+svc_status svc_whisper_content_ragged(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* utt_samples,
+                                      int T, const int32_t* frames, void* out16, int ld_out, float* feats_out,
+                                      void* stream) {
+  SVC_REQUIRE(c, "whisper_content_ragged: null context");
+  SVC_REQUIRE(wav16 && out16, "whisper_content_ragged: null %s", wav16 ? "out" : "wav16k");
+  SVC_REQUIRE(B > 0 && n >= 0 && T >= 1, "whisper_content_ragged: B=%d n_samples=%lld T=%d", B, (long long)n, T);
+  TuningScope tuning_scope_(&c->tune);
+  if (!c->finalized) {
+    set_error("context not finalized");
+    return SVC_ERR_STATE;
+  }
+  SVC_REQUIRE(c->has_whisper, "whisper weights not loaded");
+  const int D = c->wD, L = c->wctx;
+  SVC_REQUIRE(ld_out >= D, "whisper_content_ragged: ld_out=%d < D=%d", ld_out, D);
+  SVC_REQUIRE((int64_t)B * T < (1LL << 31), "whisper_content_ragged: B=%d x T=%d rows overflow the row count", B, T);
+  int64_t W64 = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tb = frames ? frames[b] : T;
+    const int64_t nb = utt_samples ? utt_samples[b] : n;
+    SVC_REQUIRE(tb >= 1 && tb <= T, "whisper_content_ragged: utterance %d: %d of %d frames", b, tb, T);
+    SVC_REQUIRE(nb >= 0 && nb <= n, "whisper_content_ragged: utterance %d: %lld of %lld samples", b, (long long)nb,
+                (long long)n);
+    W64 += svc_whisper_windows(tb);
+  }
+  SVC_REQUIRE(W64 * 3000 < (1LL << 31), "whisper_content_ragged: %lld windows overflow the row count", (long long)W64);
+  const int W = (int)W64;
+  std::vector<char> buf((size_t)W * 16 + (size_t)B * 8);
+  int64_t* wt = reinterpret_cast<int64_t*>(buf.data());
+  int* ut = reinterpret_cast<int*>(buf.data() + (size_t)W * 16);
+  int w0 = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tb = frames ? frames[b] : T;
+    const int64_t nb = utt_samples ? utt_samples[b] : n;
+    const int Wb = svc_whisper_windows(tb);
+    for (int w = 0; w < Wb; ++w) {
+      const int64_t start = Wb == 1 ? 0 : w * kWhisperWindow, cap = Wb == 1 ? kWhisperSamples : kWhisperWindow;
+      wt[2 * (w0 + w)] = (int64_t)b * n + start;
+      wt[2 * (w0 + w) + 1] = std::min(std::max<int64_t>(nb - start, 0), cap);
+    }
+    ut[2 * b] = w0;
+    ut[2 * b + 1] = tb;
+    w0 += Wb;
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_main, s);
+  void* dev = nullptr;
+  int st = c->lens_main.put(buf.data(), buf.size(), s, &dev);
+  if (st) return st;
+  float* feats = nullptr;
+  if ((st = whisper_encode_impl(c, wav16, W, n, reinterpret_cast<const int64_t*>(dev), feats_out, &feats, s))) return st;
+  const int* utab = reinterpret_cast<const int*>(reinterpret_cast<char*>(dev) + (size_t)W * 16);
+  return content_map_windows(feats, B, L, D, T, D, (f16*)out16, ld_out, utab, s, c->bf16);
 }
 
 svc_status svc_map_content(svc_ctx* c, const float* feats, int B, int src_rows, int T, int D, void* out, void* stream) {

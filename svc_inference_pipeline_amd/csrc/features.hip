@@ -96,8 +96,9 @@ __global__ __launch_bounds__(FftPlan<N>::TPF * FftPlan<N>::FR) void dft_mel_kern
   float* ml = fbs + a.fb_len;                            // [FR][n_mels] log-mel (energy)
   const int f0 = blockIdx.x * P::FR;
   const int b = blockIdx.y;
-  const float* w = a.wav + (int64_t)b * a.wav_stride;
-  const int64_t n_valid = a.nb ? a.nb[b] : a.n_valid, n_logical = a.nb ? a.nb[b] : a.n_logical;
+  const float* w = a.wav + (a.rows ? a.rows[2 * b] : (int64_t)b * a.wav_stride);
+  const int64_t n_valid = a.rows ? a.rows[2 * b + 1] : a.nb ? a.nb[b] : a.n_valid;
+  const int64_t n_logical = a.nb ? a.nb[b] : a.n_logical;
   const int n_frames = a.Tb ? min(a.n_frames, a.Tb[b]) : a.n_frames;
   if (f0 >= n_frames) return;  // block-uniform, before any barrier (zero_tail_rows clears those rows' outputs)
   const int nf = min(P::FR, n_frames - f0);
@@ -173,6 +174,7 @@ int dft_mel(const DftArgs& a, int B, hipStream_t s) {
   SVC_REQUIRE(dft_mel_supported(a.n_fft) && a.nbins == a.n_fft / 2 + 1 && a.n_frames > 0 && a.fb && a.band &&
                   a.n_mels > 0 && a.fb_len > 0 && a.twiddle,
               "dft_mel: n_fft=%d nbins=%d frames=%d mels=%d", a.n_fft, a.nbins, a.n_frames, a.n_mels);
+  SVC_REQUIRE(!(a.rows && a.nb), "dft_mel: a row table and per-utterance lengths are exclusive");
   switch (a.n_fft) {
     case 400: return launch_dft_mel<200>(a, B, s);
     case 512: return launch_dft_mel<256>(a, B, s);

@@ -20,6 +20,10 @@ struct DftArgs {
   // ragged batches (optional): utterance b has nb[b] samples (its n_valid and n_logical) and Tb[b] frames
   const int64_t* nb;
   const int* Tb;
+  // per-row table (optional, device int64 [B][2]): row b reads rows[2b + 1] valid samples starting at wav + rows[2b]
+  // (in place of wav + b * wav_stride and n_valid; n_logical stays the reflection length). The Whisper windows of a
+  // ragged batch are framed in place that way, without a gather copy
+  const int64_t* rows;
 };
 
 // windowed frames -> f64 FFT -> |X| or |X|^2 -> filterbank -> ln / log10 (-> energy), one launch

@@ -44,8 +44,16 @@ class ConvertResult:
 
 
 class SVCPipeline:
-    def __init__(self, engine: SVCEngine, f0_side=True, f0_method="parselmouth", hubert_ragged=None):
-        """hubert_ragged: a ragged batch's HuBERT / ContentVec features come from ONE padded encoder pass with
+    def __init__(self, engine: SVCEngine, f0_side=True, f0_method="parselmouth", hubert_ragged=None,
+                 whisper_ragged=None):
+        """whisper_ragged: a ragged batch's Whisper features come from ONE call (svc_whisper_content_ragged): every 30 s
+        window that exists is encoded once, short and long clips in one encoder pass, and one mapping launch writes
+        straight into the content buffer; False: the two-group form (clips of one window, then long clips padded to the
+        longest one's window count, one copy per clip; the same values bit for bit; DESIGN.md "A5-A7 for ragged
+        batches"). None (default): the one-call form with every engine that has it (SVCEngine does: its
+        `ragged_whisper` is True), the two-group form with an engine object that lacks it. True with such an engine is
+        a ValueError, never a quiet fall-back. The form in use is `self.whisper_ragged`.
+        hubert_ragged: a ragged batch's HuBERT / ContentVec features come from ONE padded encoder pass with
         per-utterance lengths (svc_hubert_encode_ragged) and one ragged mapping launch; False: one encoder pass, one
         mapping and one copy per exact-length bucket (the same values bit for bit; DESIGN.md "A8 for ragged batches").
         None (default): the one-pass form with every engine that has the length-taking entry points (SVCEngine does:
@@ -65,6 +73,11 @@ class SVCPipeline:
             raise ValueError("hubert_ragged=True: the engine has no hubert_encode(n_samples=) / map_content(frames=, "
                              "src_rows=) (its ragged_hubert is not set)")
         self.hubert_ragged = able if hubert_ragged is None else bool(hubert_ragged)
+        able = bool(getattr(engine, "ragged_whisper", False))
+        if whisper_ragged and not able:
+            raise ValueError("whisper_ragged=True: the engine has no whisper_content(wav16, n_samples, frames, T) (its "
+                             "ragged_whisper is not set)")
+        self.whisper_ragged = able if whisper_ragged is None else bool(whisper_ragged)
 
     def extract_f0(self, wav24, T, n_samples=None, T_b=None):
         """F0 by the configured method -> f64 [B, T] (rows past an utterance's T_b frames 0)."""
@@ -217,9 +230,10 @@ class SVCPipeline:
 
     def ragged_content(self, wavs16, T_b, T, wavs16_float=None):
         """Content features for a ragged batch -> f16 [B, T, D]; rows [b, :T_b[b]] equal convert()'s for that clip
-        alone. Whisper runs on zero-padded 16 kHz audio (pad_or_trim pads with zeros, so the padding is exact), in two
-        groups: clips the reference maps in one 30 s window (T_b <= 2812) and long clips (per-window, see
-        whisper_content). HuBERT / ContentVec attends over every frame and normalises over time, so it takes the
+        alone. Whisper runs on zero-padded 16 kHz audio (pad_or_trim pads with zeros, so the padding is exact): one
+        whisper_content call that encodes each clip's own windows in one pass and maps them straight into the type's
+        columns (whisper_ragged=False: two groups, clips the reference maps in one 30 s window (T_b <= 2812) and long
+        clips, per-window as in whisper_content below, each copied into place clip by clip). HuBERT / ContentVec attends over every frame and normalises over time, so it takes the
         lengths: one padded encoder pass and one mapping launch straight into its columns of the result
         (hubert_ragged=False: one pass per exact-length bucket)."""
         e = self.engine
@@ -231,7 +245,10 @@ class SVCPipeline:
         out = torch.zeros(B, T, sum(widths), device=dev, dtype=e.content_dtype)
         col = 0
         for t, w in zip(types, widths):
-            if t == "whisper":
+            if t == "whisper" and self.whisper_ragged:
+                w16, n16 = self._pad_stack(wavs16)
+                e.whisper_content(w16, n16, list(T_b), T, out=out[:, :, col:col + w])
+            elif t == "whisper":
                 for group in ([i for i in range(B) if T_b[i] <= MAX_MAPPED], [i for i in range(B) if T_b[i] > MAX_MAPPED]):
                     if not group:
                         continue

@@ -102,6 +102,7 @@ class SVCEngine:
     raises)."""
 
     ragged_hubert = True  # hubert_encode takes n_samples, map_content takes frames / src_rows (SVCPipeline)
+    ragged_whisper = True  # whisper_content encodes a ragged batch window by window in one pass (SVCPipeline)
 
     def __init__(self, cfg, device=0, whisper_state=None, mapper_state=None, vocoder_state=None, hubert_state=None,
                  hubert_output_layer=9, content_split=2, head_split=True, config=None, operands="fp16"):
@@ -269,6 +270,36 @@ class SVCEngine:
         _lib.call("svc_map_content_ex", self._ctx, _ptr(feats.contiguous()), B, S, T, D, mode,
                   ctypes.c_void_p(out.data_ptr()), out.stride(1), _stream())
         return out
+
+    def whisper_windows(self, frames):
+        """30 s Whisper windows of a clip of `frames` mel frames (svc_whisper_windows: 1 up to 2812 frames, else
+        ceil(frames / 2805))"""
+        return int(_lib.load().svc_whisper_windows(int(frames)))
+
+    def whisper_content(self, wav16, n_samples, frames, T, out=None, return_feats=False):
+        """Whisper content features of a ragged batch (svc_whisper_content_ragged): wav16 f32 [B, N16] (int16-quantised
+        16 kHz), utterance b = wav16[b, :n_samples[b]] (the rest of its row is not read) with frames[b] <= T mel frames
+        (host ints [B] each; None = N16 / T for every utterance) -> [B, T, D] in content_dtype. Every window that
+        exists is encoded once, all in one pass; rows [b, :frames[b]] equal whisper_encode + map_content on that
+        clip's own windows bit for bit, rows past them are zeros. `out` may be a column slice [B, T, D] of a wider
+        buffer, as in map_content. return_feats: also the encoder output of every window, f32 [sum of
+        whisper_windows(frames[b]), n_ctx, D], utterance-major."""
+        B, N = wav16.shape
+        d = self.whisper_dims
+        D = d["n_audio_state"]
+        if out is None:
+            out = torch.empty(B, T, D, device=wav16.device, dtype=self.content_dtype)
+        assert out.shape == (B, T, D) and out.stride(2) == 1 and out.stride(0) == T * out.stride(1)
+        assert out.dtype == self.content_dtype, f"whisper_content: out must be {self.content_dtype}"
+        fr = _host_lengths(frames, B, ctypes.c_int32)
+        feats = None
+        if return_feats:
+            n_win = sum(max(self.whisper_windows(t), 0) for t in (fr if fr is not None else [T] * B))
+            feats = torch.empty(n_win, d["n_audio_ctx"], D, device=wav16.device, dtype=torch.float32)
+        _lib.call("svc_whisper_content_ragged", self._ctx, _ptr(wav16), B, N,
+                  _host_lengths(n_samples, B, ctypes.c_int64), T, fr, ctypes.c_void_p(out.data_ptr()), out.stride(1),
+                  _ptr(feats), _stream())
+        return (out, feats) if return_feats else out
 
     def hubert_frames(self, n_samples):
         """frames of the conv feature extractor for a clip of n_samples 16 kHz samples"""
