@@ -363,7 +363,7 @@ class OperandRounding:
 
 class Fp16Operands(OperandRounding):
     """fp16 conv operands (the BigVGAN tolerance derivation), and the f16 storage of AMPBlock1's convs1 output that the
-    HIP vocoder uses (engine.hip, round 3)."""
+    HIP vocoder uses (finalize.hip, round 3)."""
 
     def __init__(self, store16=True):
         super().__init__(torch.float16, linear=False)

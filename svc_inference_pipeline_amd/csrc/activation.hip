@@ -7,6 +7,7 @@
 // sin uses v_sin_f32 on the fractional revolution of u*alpha/2pi: its error (~|u|*6e-8) is the size of the f32
 // rounding of the argument u*alpha that the reference itself incurs.
 #include "common.h"
+#include "kernels.h"
 #include "snake.h"
 
 namespace svc {

@@ -315,7 +315,7 @@ struct RingRetire {
 
 
 // One PLMS update x' = x + d (A x - Bc e'), e' = (sum_k c_k e_k) / div (modules/diffsvcrepo_inference.py:91-130;
-// engine.hip svc_diffsvc_sample, elementwise.hip plms_update).
+// stage_diffsvc.hip svc_diffsvc_sample, elementwise.hip plms_update).
 struct PlmsArgs {
   const float* e[4]; float c[4]; int ne; float div;
   float d, A, Bc;
@@ -344,6 +344,12 @@ __device__ __forceinline__ void plms_math4(const PlmsArgs& p, const float4* ev, 
   x_out = make_float4(x.x + p.d * (p.A * x.x - p.Bc * e[0]), x.y + p.d * (p.A * x.y - p.Bc * e[1]),
                       x.z + p.d * (p.A * x.z - p.Bc * e[2]), x.w + p.d * (p.A * x.w - p.Bc * e[3]));
 }
+// One DDPM p_sample update (stage_diffsvc.hip sample_impl, elementwise.hip ddpm_update)
+struct DdpmArgs {
+  float sra, srm1, c1, c2, sigma;  // sigma = exp(0.5*logvar) * (t > 0)
+  const float* z; uint64_t seed; const int* utt_ids; int step;
+  int bf16;  // x16 holds bfloat16 operands
+};
 // Kernel-selection switches: the measured production choices by default, other values select the earlier or
 // alternative kernel forms that the parity tests cover and the A/B benches compare (DESIGN.md records each result).
 // A context copies the defaults at creation, where an SVC_<NAME> environment variable overrides each (so a whole

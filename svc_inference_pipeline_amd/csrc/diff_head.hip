@@ -17,6 +17,7 @@
 // epilogue once more (its operands loaded at once, the stores undrained): bit-identical and 0.1 % slower end to end
 // (2 x 101 fewer launches, but 8 waves per CU leave the epilogue's loads latency-bound), removed.
 #include "common.h"
+#include "kernels.h"
 
 namespace svc {
 

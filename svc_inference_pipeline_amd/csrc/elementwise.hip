@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "kernels.h"
 
 namespace svc {
 
@@ -560,13 +561,7 @@ int init_noise(float* x, f16* x16, int ld16, int B, int T, int C, uint64_t seed,
 }
 
 // DDPM p_sample (modules/diffsvcrepo_inference.py:56-88), clip_denoised=True. z either given
-// (parity mode, [rows][C] already transposed from the reference's [B,1,C,T] draw) or generated.
-struct DdpmArgs {
-  float sra, srm1, c1, c2, sigma;  // sigma = exp(0.5*logvar) * (t > 0)
-  const float* z; uint64_t seed; const int* utt_ids; int step;
-  int bf16;  // x16 holds bfloat16 operands
-};
-
+// (parity mode, [rows][C] already transposed from the reference's [B,1,C,T] draw) or generated (DdpmArgs, common.h).
 __global__ void ddpm_kernel(float* x, const float* eps, f16* x16, int ld16, int T, int C, int rows, DdpmArgs a) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)rows * C) return;

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kernels.h"
 #include "fft.h"
 
 namespace svc {

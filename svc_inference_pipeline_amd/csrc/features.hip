@@ -14,6 +14,7 @@
 // f64 throughout the transform (the oracle's torch.stft is an f32 FFT; f64 keeps this side's error far below it); the
 // window multiply is f32 as in torch.stft.
 #include "common.h"
+#include "kernels.h"
 #include "spectral.h"
 #include "fft.h"
 

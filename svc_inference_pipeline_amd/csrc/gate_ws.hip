@@ -2,7 +2,7 @@
 // lines 220-227: y = dilated_conv(x + dproj) + conditioner_projection(cond); sigmoid(gate) * tanh(filter)), round 4.
 //
 // Per layer of every denoiser call: y[m][c] = sigmoid(g + cp_g) * tanh(f + cp_f), with
-//   [g | f] = conv1d_k3,dil(x16)  (K = 3 taps x 384 channels = 1152, 768 packed output columns, engine.hip pair_perm).
+//   [g | f] = conv1d_k3,dil(x16)  (K = 3 taps x 384 channels = 1152, 768 packed output columns, finalize.hip pair_perm).
 // conv_gemm4 runs this as 128 x 128 output tiles, two 4-wave workgroups per CU, each K-tile DMA'd one step ahead: every
 // tile streams its A rows and its 128 weight columns through LDS (64 FLOP per operand byte), which at the MFMA rate is the
 // whole L2 -> LDS bandwidth of a CU (64 B per clock), so its K-loop runs at ~0.4 of the MFMA peak.
@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "kernels.h"
 
 // gw_dma clobbers m0 (reserved for the compiler's own LDS-DMA and indexing uses, which all set it right before use)
 #pragma clang diagnostic ignored "-Winline-asm"

@@ -30,6 +30,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "common.h"
+#include "kernels.h"
 #include "epilogue.h"
 
 namespace svc {

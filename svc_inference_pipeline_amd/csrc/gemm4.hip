@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "kernels.h"
 #include "epilogue.h"
 
 namespace svc {

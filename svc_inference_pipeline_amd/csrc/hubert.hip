@@ -1,6 +1,6 @@
 // HuBERT / ContentVec content encoder helpers (utils/hubert.py:31-47): the pieces of
 // fairseq's HubertModel.extract_features that are not implicit GEMMs. The convolutions, projections and
-// attention reuse conv_gemm3 / conv_gemm / attention (engine.hip: svc_hubert_encode).
+// attention reuse conv_gemm3 / conv_gemm / attention (stage_content.hip: svc_hubert_encode).
 //
 //   frames5       : wav f32 [B][n] -> f16 [B][ceil(n/5)][8]: row r holds samples 5r..5r+4 (cols 5..7 zero), so
 //                   conv_layers[0] (k=10, stride 5) becomes a 2-tap stride-1 implicit GEMM over these rows.
@@ -13,6 +13,7 @@
 //   for a batch of that length alone, so its f64 partials add in the same order and scale / shift are bit-identical.
 //   layernorm_dual: LayerNorm writing both the f32 residual stream and its f16 GEMM operand (post-LN layers).
 #include "common.h"
+#include "kernels.h"
 
 namespace svc {
 

@@ -1,0 +1,98 @@
+// The host launchers of the kernel files (and the few host helpers beside them) for their callers: engine.hip, the
+// stage_*.hip files, finalize.hip and ops.hip. A launcher is declared here and nowhere else, and the file that
+// defines it includes this header too: default arguments live here only, the argument structs exist once, and a
+// definition that drifts from its declaration is a redefined default or an ambiguous call where it is compiled.
+#pragma once
+#include "common.h"
+#include "amp_conv.h"
+#include "spectral.h"
+
+namespace svc {
+
+int attention(const f16* qkv, f16* out, int B, int L, int D, hipStream_t s, bool bf16, const int* lens = nullptr);
+int layernorm_f16(const float* x, const float* g, const float* b, f16* y, int rows, int D, int ldy, hipStream_t s,
+                  bool bf);
+int layernorm_f32(const float* x, const float* g, const float* b, float* y, int rows, int D, int ldy, hipStream_t s);
+int activation1d(const float* x, f16* y, int B, int L, int C, int ldy, const float* alpha_log, const float* beta_log,
+                 const float* filt, hipStream_t s, const int* tv = nullptr, int tv_mul = 1, const f16* x16 = nullptr);
+int f32_to_f16(const float* x, int ldx, f16* y, int ldy, int rows, int C, int Cpad, hipStream_t s, bool bf);
+int denorm_mel(const float* x, f16* y, float* y32, int ldy, int rows, int C, const float* mn, const float* mx,
+               hipStream_t s);
+int content_map(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst, hipStream_t s,
+                bool bf);
+int bucketize(const double* f0, const float* en, const float* mbins, const float* ebins, int nb, int* im, int* ie,
+              int n, hipStream_t s);
+int plms_update(const PlmsArgs& p, int rows, int C, hipStream_t s);
+int ddpm_update(float* x, const float* eps, f16* x16, int ld16, int B, int T, int C, const DdpmArgs& a, hipStream_t s);
+int init_noise(float* x, f16* x16, int ld16, int B, int T, int C, uint64_t seed, const int* utt_ids, float std,
+               hipStream_t s, bool bf);
+int conv_post(const f16* a, int lda, int B, int L, int C, const float* w, float bias, const float* fade, int nfade,
+              float* out, hipStream_t s, const int* tv = nullptr, int tv_mul = 1);
+int zero_tail_rows(float* x, int B, int T, int C, const int* Tb, hipStream_t s);
+int whisper_normalize(const float* logspec, float* mx_scratch, f16* out, int B, int64_t n_per_utt, hipStream_t s,
+                      int split_c, bool bf, int ldo);
+int layernorm_f16x3(const float* x, const float* g, const float* b, f16* y, int rows, int D, hipStream_t s, bool bf);
+int f32_to_f16x3_grouped(const float* x, f16* y, int rows, int C, int Cg, hipStream_t s, bool bf);
+int f16_to_f32(const f16* x, float* y, int64_t n, hipStream_t s);
+int f32_to_f16x3(const float* x, int ldx, f16* y, int rows, int C, hipStream_t s, bool bf);
+int conv_gemm3(const ConvGemmArgs& a, const EpiArgs& e, const f16* zpage, int variant, hipStream_t s);
+int conv_gemm4(const ConvGemmArgs& a, const EpiArgs& e, const f16* zpage, hipStream_t s, bool direct_gate);
+bool gate_ws_fits(const ConvGemmArgs& a, const EpiArgs& e);
+extern unsigned long long* gate_ws_stamps;
+int gate_ws_nstamp();
+int gate_ws(const ConvGemmArgs& a, const EpiArgs& e, hipStream_t s);
+int gate_ws_pack(const f16* W, int ldw, f16* Wf, hipStream_t s);
+size_t gate_ws_pack_elems();
+int res_proj(const f16* g, const f16* Wf, const float* bias, const float* sub, const float* add, float div, f16* hi,
+             f16* lo, int M, bool bf16, int lanes_cap, hipStream_t s);
+int res_proj_pack(const f16* W, int ldw, f16* Wf, hipStream_t s);
+size_t res_proj_pack_elems();
+int mel_proj(const f16* x, int ldx, const f16* Wf, const float* bias, const float* add, f16* hi, f16* lo, int M,
+             bool bf16, hipStream_t s);
+int mel_proj_pack(const f16* W, int ldw, f16* Wf, hipStream_t s);
+size_t mel_proj_pack_elems();
+int diff_head(const f16* s16, const f16* Wsp, const float* bsp, int Nsp, int Ksp, const f16* Wout, const float* bout,
+              int Nout, int Kout, int Npad_out, float* eps, int ld_eps, int M, const f16* zpage, hipStream_t s,
+              bool bf16);
+int pitch_shift(double* f0, int B, int T, double target, hipStream_t s);
+int content_map_hubert(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                       hipStream_t s, bool bf);
+int content_map_ragged(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                       const int* tab, hipStream_t s, bool bf);
+int content_map_windows(const float* src, int B, int win_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
+                        const int* tab, hipStream_t s, bool bf);
+int zero_tail_rows16(f16* x, int B, int T, int ld, const int* Tb, int max_tail, hipStream_t s);
+int hubert_frames5(const float* wav, int B, int64_t n, f16* out, bool split, hipStream_t s, bool bf,
+                   const int64_t* nb = nullptr);
+int groupnorm_gelu(const float* x, int B, int T, int C, const float* gamma, const float* beta, double* part,
+                   int max_chunks, float2* ss, f16* y, bool split, hipStream_t s, bool bf, const int* Tb = nullptr,
+                   int nck_max = 0);
+int layernorm_dual(const float* x, const float* g, const float* b, float* y32, f16* y16, int rows, int D, bool split,
+                   hipStream_t s, bool bf);
+int pack_qkv(const float* q, const float* k, const float* v, f16* qkv, int64_t rows, int D, float scale, hipStream_t s);
+int f0_praat_ac(const float* wav, int B, int64_t n_samples, double fs, double time_step, double floor_hz,
+                double ceiling_hz, double voicing, int T, double* f0_out, void* workspace, size_t ws_bytes,
+                const double* tables, hipStream_t s, const int64_t* n_b = nullptr, const int* T_b = nullptr,
+                StageRing* ring = nullptr);
+size_t f0_workspace_bytes(int B, int64_t n_samples, double fs, double time_step, double floor_hz);
+size_t f0_table_doubles(double fs, double floor_hz);
+int f0_tables(double fs, double floor_hz, double* out);
+size_t pyin_table_doubles(double sr, double fmin, double fmax, int frame_length, int win_length, int hop);
+size_t pyin_workspace_bytes(int B, int F, double sr, double fmin, double fmax, int frame_length, int win_length,
+                            int hop);
+int pyin_tables(double sr, double fmin, double fmax, int frame_length, int win_length, int hop, double* out);
+int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, const int64_t* nvalid_host, double sr,
+            double fmin, double fmax, int frame_length, int win_length, int hop, int F, double* f0, void* ws,
+            size_t ws_bytes, const double* tables_dev, hipStream_t s);
+size_t pcm16_table_bytes(int B);
+int pcm16(const float* wav, int B, int64_t S, void* table, int64_t max_nb, int sil, int64_t L, int turn_up,
+          double volume_peak, int16_t* pcm, float* peak_out, int need_peak, hipStream_t s);
+int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+             const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
+             float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info, hipStream_t s);
+// resample.hip: the cached plan of a rate pair (design_plan's integers) and its taps once more in phase-major order on
+// the device, hpm[k0 * per_phase + r] = h[k0 + up * r] (per_phase = (taps - 1) / up + 1); 0, or -1 when the upload failed
+int get_plan_pm(int sr_in, int sr_out, const double** hpm, int* up, int* down, int* pre_remove, int* taps,
+                int* per_phase);
+
+}  // namespace svc

@@ -22,16 +22,12 @@
 // are contiguous. Outputs past the utterance's own length are written as zeros.
 #include "../../include/svc_hip.h"
 #include "common.h"
+#include "kernels.h"
 
 #include <numeric>
 #include <vector>
 
 namespace svc {
-
-// resample.hip: the cached plan of a rate pair (design_plan's integers) and its taps once more in phase-major order on
-// the device, hpm[k0 * per_phase + r] = h[k0 + up * r] (per_phase = (taps - 1) / up + 1); 0, or -1 when the upload failed
-int get_plan_pm(int sr_in, int sr_out, const double** hpm, int* up, int* down, int* pre_remove, int* taps,
-                int* per_phase);
 
 namespace {
 
@@ -227,7 +223,7 @@ RatePlan rate_plan(int sr_in, int sr_out) {
 
 }  // namespace
 
-// The host half of svc_load_pcm (engine.hip owns the context and its ring): argument checks before any HIP call, one
+// The host half of svc_load_pcm (stage_features.hip owns the context and its ring): argument checks before any HIP call, one
 // staged table [PcmUtt x B | PcmPlan x n_plans | zeroed peak words], then the launches. `ring` and `device` point into
 // the context and are read only after the checks.
 int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,

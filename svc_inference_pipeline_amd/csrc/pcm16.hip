@@ -9,6 +9,7 @@
 // (peak 0) gives zeros where the host function divides by zero; non-finite input is undefined (svc_hip.h).
 #include "../../include/svc_hip.h"
 #include "common.h"
+#include "kernels.h"
 
 namespace svc {
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kernels.h"
 
 namespace svc {
 

@@ -1,6 +1,6 @@
 // DiffSVC residual projection as a weight-stationary row stream (modules/diffsvc.py:228-232), round 3.
 //
-// Per layer i < 19 of every denoiser call the split residual stream x + dproj_i = hi + lo (two fp16 halves, engine.hip
+// Per layer i < 19 of every denoiser call the split residual stream x + dproj_i = hi + lo (two fp16 halves, stage_diffsvc.hip
 // denoise) is updated in place from the layer's gate output g (f16 [M][384]):
 //   v  = g W_res^T + b_res                                    (residual half of output_projection, K = N = 384)
 //   x' = (((hi + lo) - dproj_i) + v) / sqrt(2)                (modules/diffsvc.py:232)
@@ -23,6 +23,7 @@
 // K order (k = 0..383 in 32-deep MFMA steps into one accumulator) and the epilogue's arithmetic are conv_gemm3's, so the
 // result is bit-identical to the tiled GEMM with its LDS-staged split epilogue (tests/test_gpu_ops.py).
 #include "common.h"
+#include "kernels.h"
 
 // rp_dma clobbers m0 (reserved for the compiler's own LDS-DMA and indexing uses, which all set it right before use)
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -193,7 +194,7 @@ __global__ __launch_bounds__(RP_NT, 1) void res_proj_kernel(ResProjArgs p) {
 #pragma unroll
     for (int kc = 0; kc < 12; ++kc)  // acc[r] = C[row fr][n0 + 4 fk + r]
       acc = O::mfma(w[kc], *reinterpret_cast<const half8*>(slot + rp_gchunk(fr, kc * 4 + fk) * 16), acc);
-    // split-residual update (engine.hip epilogue_pass arithmetic, same order)
+    // split-residual update (epilogue.h epilogue_pass arithmetic, same order)
     const float v[4] = {acc[0] + bi.x, acc[1] + bi.y, acc[2] + bi.z, acc[3] + bi.w};
     const float s4[4] = {sb.x, sb.y, sb.z, sb.w}, a4[4] = {ad.x, ad.y, ad.z, ad.w};
 #pragma unroll
@@ -279,7 +280,7 @@ int res_proj(const f16* g, const f16* Wf, const float* bias, const float* sub, c
 // ---------------------------------------------------------------------------- input projection (round 5)
 // The denoiser's first step (modules/diffsvc.py:299-300, mel_preprocess: Conv1d(n_mel -> 384, 1) then ReLU) writes
 // the split residual stream's first value: h = relu(x W_mel^T + b), hi = f16(h + dproj_0), lo = f16((h + dproj_0) - hi)
-// (engine.hip denoise). K = 100 against 1536 B of hi / lo out per row: a store stream of 52 MB per sampler call, which
+// (stage_diffsvc.hip denoise). K = 100 against 1536 B of hi / lo out per row: a store stream of 52 MB per sampler call, which
 // conv_gemm3's 128 x 128 tiles ran at MFMA busy 0.04 with 36 VALU per MFMA (24 us per launch).
 // Here one workgroup per CU walks 16-row tiles:
 //   * W_mel (384 x 128 f16, zero past k = 100) lives in VGPRs: each of 12 compute waves holds its 32 output columns as

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.h"
+#include "kernels.h"
 #include "svc_hip.h"
 
 namespace svc {

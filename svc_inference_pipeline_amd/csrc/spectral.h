@@ -1,4 +1,4 @@
-// Spectral front-end launch arguments (features.hip), shared with engine.hip.
+// Spectral front-end launch arguments (features.hip), shared with the stage files that launch it.
 #pragma once
 #include "common.h"
 

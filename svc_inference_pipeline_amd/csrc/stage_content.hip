@@ -1,0 +1,504 @@
+// The content encoders (Whisper, HuBERT / ContentVec), their frame mappings and the conditioner.
+#include <math.h>
+#include <stdlib.h>
+
+#include "engine.h"
+
+extern "C" {
+
+// ---------------------------------------------------------------------------- whisper
+static const int64_t kWhisperSamples = 480000;  // utils/whisper_extractor/audio.py:18 (30 s @ 16 kHz)
+static const int64_t kWhisperWindow = 478720;   // samples per window of a long clip: 29.92 s = 1496 encoder rows
+static const int kWindowFrames = 2805;          // = 1496 * 15 / 8 mel frames, so every window starts on a mel frame
+static const int kMaxMapped = 2812;             // utils/whisper.py:56 (1500 * 15 // 8): the single 30 s window's frames
+
+// The encoder over B 30 s windows. rows (device int64 [B][2], or NULL): window b holds rows[2b + 1] samples starting at
+// wav16 + rows[2b] (DftArgs::rows), zeros after them; NULL is the uniform batch, window b = wav16[b][0 .. min(n, 30 s)).
+// feats f32 [B][n_ctx][n_state], or NULL: taken from the workspace; *feats_used receives the buffer either way.
+static int whisper_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* rows, float* feats,
+                               float** feats_used, hipStream_t s) {
+  SVC_REQUIRE(c->has_whisper, "whisper weights not loaded");
+  const int64_t NS = kWhisperSamples;
+  const int F = 3000, D = c->wD, L = c->wctx;
+  SVC_REQUIRE(B > 0 && (rows || n > 0), "whisper: B=%d n=%lld", B, (long long)n);
+  SVC_REQUIRE(L * 2 == F, "whisper: n_ctx %d != 1500", L);
+  SVC_REQUIRE((int64_t)B * F < (1LL << 31), "whisper: %d windows of %d rows overflow the row count", B, F);
+  const int nb = 201;
+  const size_t rows1 = (size_t)B * F, rows2 = (size_t)B * L;
+  const int X3 = c->content_split ? 3 : 1;  // split-fp16 block operands are [hi | lo | hi] rows
+  const int XS = c->content_mode != 0 ? 3 : 1;  // the conv stem is split-fp16 in both split modes
+  const int LDM = XS == 3 ? c->wstem_ld : c->wmels;  // the stem operand's row stride
+  size_t need = rows1 * c->wmels * 4 + rows1 * LDM * 2 + rows1 * D * 2 * XS /*h1*/ +
+                rows2 * D * 4 + rows2 * D * 2 * X3 + rows2 * 3 * D * 2 + rows2 * D * 2 + rows2 * 4 * D * 2 * X3 + 64 * 4096;
+  if (!feats) need += rows2 * D * 4 + 4096;
+  int st;
+  if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
+  c->ws.reset();
+  if (!feats) {
+    WS_GET(float, fws, rows2 * D);
+    feats = fws;
+  }
+  if (feats_used) *feats_used = feats;
+  WS_GET(float, ls, rows1 * c->wmels);
+  WS_GET(f16, lm16, rows1 * LDM);
+  WS_GET(float, mx, B);
+  DftArgs a{};
+  a.wav = wav16;
+  a.wav_stride = n;
+  a.n_valid = std::min<int64_t>(n, NS);
+  a.n_logical = NS;
+  a.rows = rows;
+  a.n_fft = 400;
+  a.hop = 160;
+  a.pad = 200;
+  a.n_frames = F;
+  a.nbins = nb;
+  a.window = c->win16;
+  a.twiddle = reinterpret_cast<const double2*>(c->tw16);
+  a.mode = 1;
+  a.fb = c->fb16;
+  a.band = c->band16;
+  a.fb_len = c->fb16_len;
+  a.n_mels = c->wmels;
+  a.out = ls;
+  if ((st = dft_mel(a, B, s))) return st;
+  if ((st = whisper_normalize(ls, mx, lm16, B, (int64_t)F * c->wmels, s, XS == 3 ? c->wmels : 0, c->bf16, LDM)))
+    return st;
+  // conv stem
+  WS_GET(f16, h1, rows1 * D * XS);
+  EpiArgs e = epi();
+  e.act = ACT_GELU;
+  e.out16 = h1;
+  e.ld16 = D * XS;
+  e.split16 = XS == 3 ? D : 0;
+  if ((st = run_gemm(c->wconv1, lm16, LDM, LDM, B, F, F, e, s, "whisper.conv1"))) return st;
+  WS_GET(float, x, rows2 * D);
+  e = epi();
+  e.act = ACT_GELU;
+  e.add_t = c->wpos;
+  e.ld_add_t = D;
+  e.out32 = x;
+  e.ld32 = D;
+  if ((st = run_gemm(c->wconv2, h1, D * XS, D * XS, B, F, L, e, s, "whisper.conv2"))) return st;
+  WS_GET(f16, n16, rows2 * D * X3);
+  WS_GET(f16, qkv, rows2 * 3 * D);
+  WS_GET(f16, o16, rows2 * D);
+  WS_GET(f16, h16, rows2 * 4 * D * X3);
+  const float qk_scale = powf((float)(D / c->wH), -0.25f);
+  // whisper_streams = n > 1 runs the 24 blocks as utterance-aligned sub-batches on n streams (as the sampler
+  // does): rows are time-major per utterance, so a sub-batch is a row range of every buffer, and one sub-batch's
+  // HBM-bound GEMM epilogues / layer norms run beside the other's MFMA phases. Default 1: with the F0 stage on its
+  // side stream the single full-batch stream measured 0.3-0.4 % faster end to end (three A/B pairs, r01i kernels).
+  SubBatches sb;
+  if ((st = sb.fork(c, tuning().whisper_streams, B, s))) return st;
+  for (int i = 0; i < c->wL; ++i) {
+    WBlock& b = c->wblocks[i];
+    for (int h = 0; h < sb.n; ++h) {
+      const int b0 = sb.b0(h), Bh = sb.b0(h + 1) - b0;
+      const size_t r = (size_t)b0 * L, rows_h = (size_t)Bh * L;
+      hipStream_t hs = sb.stream(h);
+      float* xh = x + r * D;
+      f16* n16h = n16 + r * D * X3;
+      f16* qkvh = qkv + r * 3 * D;
+      f16* o16h = o16 + r * D;
+      f16* h16h = h16 + r * 4 * D * X3;
+      auto ln16 = [&](const float* g, const float* bb) {
+        return X3 == 3 ? layernorm_f16x3(xh, g, bb, n16h, (int)rows_h, D, hs, c->bf16)
+                       : layernorm_f16(xh, g, bb, n16h, (int)rows_h, D, D, hs, c->bf16);
+      };
+      if ((st = ln16(b.ln1_g, b.ln1_b))) return st;
+      e = epi();
+      e.out16 = qkvh;
+      e.ld16 = 3 * D;
+      e.scale_cols = 2 * D;
+      e.col_scale = qk_scale;
+      e.scale_cols2 = D;  // q also carries log2(e): the attention kernel's scores are in exp2 units
+      e.col_scale2 = qk_scale * ATT_LOG2E;
+      if ((st = run_gemm(b.qkv, n16h, D * X3, D * X3, Bh, L, L, e, hs, "whisper.qkv"))) return st;
+      if (b.split_v) {
+        e = epi();
+        e.out16 = qkvh + 2 * D;
+        e.ld16 = 3 * D;
+        if ((st = run_gemm(b.v, n16h, D * X3, D * X3, Bh, L, L, e, hs, "whisper.v"))) return st;
+      }
+      if ((st = attention(qkvh, o16h, Bh, L, D, hs, c->bf16))) return st;
+      e = epi();
+      e.add_row = xh;
+      e.ld_add_row = D;
+      e.out32 = xh;
+      e.ld32 = D;
+      if ((st = run_gemm(b.out, o16h, D, D, Bh, L, L, e, hs, "whisper.out"))) return st;
+      if ((st = ln16(b.ln2_g, b.ln2_b))) return st;
+      e = epi();
+      e.act = ACT_GELU;
+      e.out16 = h16h;
+      e.ld16 = 4 * D * X3;
+      e.split16 = X3 == 3 ? 4 * D : 0;
+      if ((st = run_gemm(b.fc1, n16h, D * X3, D * X3, Bh, L, L, e, hs, "whisper.fc1"))) return st;
+      e = epi();
+      e.add_row = xh;
+      e.ld_add_row = D;
+      e.out32 = xh;
+      e.ld32 = D;
+      if ((st = run_gemm(b.fc2, h16h, 4 * D * X3, 4 * D * X3, Bh, L, L, e, hs, "whisper.fc2"))) return st;
+    }
+  }
+  if ((st = sb.join())) return st;
+  return layernorm_f32(x, c->wlnp_g, c->wlnp_b, feats, (int)rows2, D, D, s);
+}
+
+svc_status svc_whisper_encode(svc_ctx* c, const float* wav16, int B, int64_t n, float* feats, void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(feats, "whisper: null feats");
+  return whisper_encode_impl(c, wav16, B, n, nullptr, feats, nullptr, (hipStream_t)stream);
+}
+
+int svc_whisper_windows(int frames) {
+  if (frames < 1) return -1;
+  return frames <= kMaxMapped ? 1 : (frames - 1) / kWindowFrames + 1;
+}
+
+// A ragged Whisper batch: every window that exists goes through the encoder once, in one pass, framed in place from
+// the padded batch through the per-window table; one mapping launch writes each utterance's frames from its own
+// windows. Table in the main length ring: int64 [W][2] (source offset, valid samples), then int32 [B][2] (first
+// window, frames).
+svc_status svc_whisper_content_ragged(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* utt_samples,
+                                      int T, const int32_t* frames, void* out16, int ld_out, float* feats_out,
+                                      void* stream) {
+  SVC_REQUIRE(c, "whisper_content_ragged: null context");
+  SVC_REQUIRE(wav16 && out16, "whisper_content_ragged: null %s", wav16 ? "out" : "wav16k");
+  SVC_REQUIRE(B > 0 && n >= 0 && T >= 1, "whisper_content_ragged: B=%d n_samples=%lld T=%d", B, (long long)n, T);
+  TuningScope tuning_scope_(&c->tune);
+  if (!c->finalized) {
+    set_error("context not finalized");
+    return SVC_ERR_STATE;
+  }
+  SVC_REQUIRE(c->has_whisper, "whisper weights not loaded");
+  const int D = c->wD, L = c->wctx;
+  SVC_REQUIRE(ld_out >= D, "whisper_content_ragged: ld_out=%d < D=%d", ld_out, D);
+  SVC_REQUIRE((int64_t)B * T < (1LL << 31), "whisper_content_ragged: B=%d x T=%d rows overflow the row count", B, T);
+  int64_t W64 = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tb = frames ? frames[b] : T;
+    const int64_t nb = utt_samples ? utt_samples[b] : n;
+    SVC_REQUIRE(tb >= 1 && tb <= T, "whisper_content_ragged: utterance %d: %d of %d frames", b, tb, T);
+    SVC_REQUIRE(nb >= 0 && nb <= n, "whisper_content_ragged: utterance %d: %lld of %lld samples", b, (long long)nb,
+                (long long)n);
+    W64 += svc_whisper_windows(tb);
+  }
+  SVC_REQUIRE(W64 * 3000 < (1LL << 31), "whisper_content_ragged: %lld windows overflow the row count", (long long)W64);
+  const int W = (int)W64;
+  std::vector<char> buf((size_t)W * 16 + (size_t)B * 8);
+  int64_t* wt = reinterpret_cast<int64_t*>(buf.data());
+  int* ut = reinterpret_cast<int*>(buf.data() + (size_t)W * 16);
+  int w0 = 0;
+  for (int b = 0; b < B; ++b) {
+    const int tb = frames ? frames[b] : T;
+    const int64_t nb = utt_samples ? utt_samples[b] : n;
+    const int Wb = svc_whisper_windows(tb);
+    for (int w = 0; w < Wb; ++w) {
+      const int64_t start = Wb == 1 ? 0 : w * kWhisperWindow, cap = Wb == 1 ? kWhisperSamples : kWhisperWindow;
+      wt[2 * (w0 + w)] = (int64_t)b * n + start;
+      wt[2 * (w0 + w) + 1] = std::min(std::max<int64_t>(nb - start, 0), cap);
+    }
+    ut[2 * b] = w0;
+    ut[2 * b + 1] = tb;
+    w0 += Wb;
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_main, s);
+  void* dev = nullptr;
+  int st = c->lens_main.put(buf.data(), buf.size(), s, &dev);
+  if (st) return st;
+  float* feats = nullptr;
+  if ((st = whisper_encode_impl(c, wav16, W, n, reinterpret_cast<const int64_t*>(dev), feats_out, &feats, s))) return st;
+  const int* utab = reinterpret_cast<const int*>(reinterpret_cast<char*>(dev) + (size_t)W * 16);
+  return content_map_windows(feats, B, L, D, T, D, (f16*)out16, ld_out, utab, s, c->bf16);
+}
+
+svc_status svc_map_content(svc_ctx* c, const float* feats, int B, int src_rows, int T, int D, void* out, void* stream) {
+  SVC_REQUIRE(c && feats && out, "map_content: null");
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  return content_map(feats, B, src_rows, D, T, D, (f16*)out, D, (hipStream_t)stream, c->bf16);
+}
+
+svc_status svc_map_content_ex(svc_ctx* c, const float* feats, int B, int src_rows, int T, int D, int mode, void* out,
+                              int ld_out, void* stream) {
+  SVC_REQUIRE(c && feats && out && B > 0 && D > 0 && ld_out >= D, "map_content_ex: bad args");
+  SVC_REQUIRE(mode == 0 || mode == 1, "map_content_ex: mode %d", mode);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  if (mode == 0) return content_map(feats, B, src_rows, D, T, D, (f16*)out, ld_out, (hipStream_t)stream, c->bf16);
+  return content_map_hubert(feats, B, src_rows, D, T, D, (f16*)out, ld_out, (hipStream_t)stream, c->bf16);
+}
+
+svc_status svc_map_content_ragged(svc_ctx* c, const float* feats, int B, int src_rows, const int32_t* utt_src_rows,
+                                  int T, const int32_t* frames, int D, int mode, void* out, int ld_out, void* stream) {
+  SVC_REQUIRE(c, "map_content_ragged: null context");
+  SVC_REQUIRE(feats && out && B > 0 && D > 0 && ld_out >= D && src_rows >= 1 && T >= 1,
+              "map_content_ragged: bad args (B=%d src_rows=%d T=%d D=%d ld_out=%d)", B, src_rows, T, D, ld_out);
+  SVC_REQUIRE(mode == 0 || mode == 1, "map_content_ragged: mode %d", mode);
+  if (!utt_src_rows && !frames) return svc_map_content_ex(c, feats, B, src_rows, T, D, mode, out, ld_out, stream);
+  // each utterance is checked as content_map / content_map_hubert check a batch of its shape, before any HIP call
+  std::vector<int> tab((size_t)2 * B);
+  for (int b = 0; b < B; ++b) {
+    const int sb = utt_src_rows ? utt_src_rows[b] : src_rows, tb = frames ? frames[b] : T;
+    SVC_REQUIRE(sb >= 1 && sb <= src_rows && tb >= 1 && tb <= T,
+                "map_content_ragged: utterance %d: %d of %d source rows, %d of %d frames", b, sb, src_rows, tb, T);
+    if (mode == 0) {
+      SVC_REQUIRE(tb <= 2812 && tb * 8 / 15 + 1 <= sb, "content_map: utterance %d: T=%d src_rows=%d", b, tb, sb);
+      tab[B + b] = tb;
+    } else {
+      const int n_down = (int)((int64_t)sb * 15 / 8);
+      SVC_REQUIRE(n_down >= 1 && std::abs(tb - n_down) <= 3,
+                  "content_map_hubert: utterance %d: %d content frames map to %d rows but T=%d (|diff| > 3; "
+                  "utils/hubert.py:114-120)", b, sb, n_down, tb);
+      tab[B + b] = n_down;
+    }
+    tab[b] = tb;
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_main, s);
+  void* dev = nullptr;
+  int st = c->lens_main.put(tab.data(), tab.size() * sizeof(int), s, &dev);
+  if (st) return st;
+  return content_map_ragged(feats, B, src_rows, D, T, D, (f16*)out, ld_out, (const int*)dev, s, c->bf16);
+}
+
+// ---------------------------------------------------------------------------- hubert / contentvec (A8)
+static int64_t hubert_len(int64_t n, int upto) {
+  static const int k[7] = {10, 3, 3, 3, 3, 2, 2}, st[7] = {5, 2, 2, 2, 2, 2, 2};
+  for (int i = 0; i < upto; ++i) n = n < k[i] ? 0 : (n - k[i]) / st[i] + 1;
+  return n;
+}
+
+// utt (host int64 [B], validated by the caller, or NULL): ragged batch. Three things look across time and take the
+// utterance's own length: the GroupNorm statistics (its own t1 rows and chunk partition), the positional conv (its
+// 16-bit input operand is zeroed from row F_b on, the zero padding the clip has alone) and the attention (keys and
+// queries stop at F_b). The valid convs make frame i < F_b depend on samples < n_b only and the GEMMs and LayerNorms
+// are row-wise, so they run over the padded batch unchanged; rows >= F_b of feats are zeroed at the end.
+static int hubert_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* utt, float* feats,
+                              hipStream_t s) {
+  SVC_REQUIRE(c->has_hubert, "hubert weights not loaded");
+  const int64_t F64 = hubert_len(n, 7);
+  SVC_REQUIRE(B > 0 && F64 >= 1 && (int64_t)B * hubert_len(n, 1) < (1LL << 31), "hubert: B=%d n=%lld", B,
+              (long long)n);
+  int64_t t[8];
+  for (int i = 0; i <= 7; ++i) t[i] = hubert_len(n, i);  // t[0] = n samples, t[7] = frames
+  const int Cc = c->hC, D = c->hD, F = (int)F64;
+  const int Fd = c->hblocks[0].fc1.N;
+  const bool sp = c->content_mode != 0;  // HuBERT: split-fp16 in both split modes
+  const int X3 = sp ? 3 : 1;  // split-fp16 operands are [hi | lo | hi] rows
+  const int w5 = sp ? 16 : 8;
+  const int64_t R5 = cdiv64(n, 5);
+  const size_t rows0 = (size_t)B * t[1], rowsF = (size_t)B * F;
+  const int kChunks = 64;
+  size_t need = (size_t)B * R5 * w5 * 2 + rows0 * Cc * 4 + rows0 * Cc * 2 * X3 + (size_t)B * kChunks * Cc * 16 +
+                (size_t)B * Cc * 8 + (size_t)B * (t[2] + t[3]) * Cc * 2 * X3 + rowsF * Cc * (4 + 2 * X3) +
+                rowsF * D * (4 + 2 * X3) + rowsF * 3 * D * 2 + rowsF * D * 2 + rowsF * Fd * 2 * X3 + 32 * 4096;
+  int st;
+  // per-utterance tables: samples (int64 [B]), then conv_layers[0] rows t1 and frames F (int32 [B] each)
+  const int64_t* nb_dev = nullptr;
+  const int *t1_dev = nullptr, *F_dev = nullptr;
+  int nck_max = 0, F_min = F;
+  RingRetire retire_(c->lens_main, s);
+  if (utt) {
+    std::vector<char> buf((size_t)B * 16);
+    int64_t* nv = reinterpret_cast<int64_t*>(buf.data());
+    int* tv = reinterpret_cast<int*>(buf.data() + (size_t)B * 8);
+    for (int b = 0; b < B; ++b) {
+      nv[b] = utt[b];
+      tv[b] = (int)hubert_len(utt[b], 1);
+      tv[B + b] = (int)hubert_len(utt[b], 7);
+      F_min = std::min(F_min, tv[B + b]);
+      const int chunks = std::max(1, std::min(kChunks, cdiv(tv[b], 256)));
+      nck_max = std::max(nck_max, cdiv(tv[b], cdiv(tv[b], chunks)));
+    }
+    void* dev = nullptr;
+    if ((st = c->lens_main.put(buf.data(), buf.size(), s, &dev))) return st;
+    nb_dev = reinterpret_cast<const int64_t*>(dev);
+    t1_dev = reinterpret_cast<const int*>(reinterpret_cast<char*>(dev) + (size_t)B * 8);
+    F_dev = t1_dev + B;
+  }
+  if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
+  c->ws.reset();
+  // ---- feature extractor (wav2vec2 ConvFeatureExtractionModel, mode "default")
+  WS_GET(f16, f5, (size_t)B * R5 * w5);
+  WS_GET(float, c0, rows0 * Cc);
+  WS_GET(f16, g16, rows0 * Cc * X3);
+  WS_GET(double, part, (size_t)B * kChunks * Cc * 2);
+  WS_GET(float2, gss, (size_t)B * Cc);
+  WS_GET(f16, pa, (size_t)B * t[2] * Cc * X3);
+  WS_GET(f16, pb, (size_t)B * t[3] * Cc * X3);
+  WS_GET(float, c6, rowsF * Cc);
+  WS_GET(f16, ln16, rowsF * Cc * X3);
+  if ((st = hubert_frames5(wav16, B, n, f5, sp, s, c->bf16, nb_dev))) return st;
+  EpiArgs e = epi();
+  e.out32 = c0;
+  e.ld32 = Cc;
+  if ((st = run_gemm(c->hconv[0], f5, w5, w5, B, (int)R5, (int)t[1], e, s, "hubert.conv0"))) return st;
+  if ((st = groupnorm_gelu(c0, B, (int)t[1], Cc, c->hgn_g, c->hgn_b, part, kChunks, gss, g16, sp, s, c->bf16, t1_dev,
+                           nck_max)))
+    return st;
+  const f16* in = g16;
+  for (int i = 1; i < 7; ++i) {
+    e = epi();
+    e.act = ACT_GELU;
+    if (i == 6) {
+      e.out32 = c6;
+      e.ld32 = Cc;
+    } else {
+      e.out16 = (i & 1) ? pa : pb;
+      e.ld16 = Cc * X3;
+      e.split16 = sp ? Cc : 0;
+    }
+    if ((st = run_gemm(c->hconv[i], in, Cc * X3, Cc * X3, B, (int)t[i], (int)t[i + 1], e, s, "hubert.convs"))) return st;
+    in = e.out16;
+  }
+  // ---- HubertModel.forward_features tail: LayerNorm(C) -> post_extract_proj
+  if ((st = sp ? layernorm_f16x3(c6, c->hln_g, c->hln_b, ln16, (int)rowsF, Cc, s, c->bf16)
+               : layernorm_f16(c6, c->hln_g, c->hln_b, ln16, (int)rowsF, Cc, Cc, s, c->bf16)))
+    return st;
+  WS_GET(float, x, rowsF * D);
+  WS_GET(f16, x16, rowsF * D * X3);
+  e = epi();
+  e.out32 = x;
+  e.ld32 = D;
+  if (!sp) {
+    e.out16 = x16;
+    e.ld16 = D;
+  }
+  if ((st = run_gemm(c->hproj, ln16, Cc * X3, Cc * X3, B, F, F, e, s, "hubert.proj"))) return st;
+  // ---- TransformerEncoder: x += GELU(pos_conv(x)) per group, then LayerNorm (layer_norm_first = False)
+  const int Cg = D / c->hPosG;
+  if (sp && (st = f32_to_f16x3_grouped(x, x16, (int)rowsF, D, Cg, s, c->bf16))) return st;  // group g: [hi | lo | hi] x Cg
+  // ragged: pos_conv (k = 128, pad 64) reads up to 64 rows past an utterance's end, which alone are its zero padding.
+  // Only the padding rows of the operand are rewritten (the projection's f32 output x keeps them: row-wise from here)
+  if (F_dev && (st = zero_tail_rows16(x16, B, F, D * X3, F_dev, F - F_min, s))) return st;
+  for (int gi = 0; gi < c->hPosG; ++gi) {
+    e = epi();
+    e.act = ACT_GELU;
+    e.add_row = x + gi * Cg;
+    e.ld_add_row = D;
+    e.out32 = x + gi * Cg;
+    e.ld32 = D;
+    if ((st = run_gemm(c->hpos[gi], x16 + (size_t)gi * Cg * X3, D * X3, Cg * X3, B, F, F, e, s, "hubert.pos_conv")))
+      return st;
+  }
+  if ((st = layernorm_dual(x, c->henc_ln_g, c->henc_ln_b, x, x16, (int)rowsF, D, sp, s, c->bf16))) return st;
+  WS_GET(f16, qkv, rowsF * 3 * D);
+  WS_GET(f16, o16, rowsF * D);
+  WS_GET(f16, h16, rowsF * Fd * X3);
+  const float qk_scale = powf(64.0f, -0.25f);  // q * dh^-1/2 split over q and k
+  for (int i = 0; i < c->hLayers; ++i) {
+    HBlock& b = c->hblocks[i];
+    e = epi();
+    e.out16 = qkv;
+    e.ld16 = 3 * D;
+    e.scale_cols = 2 * D;
+    e.col_scale = qk_scale;
+    e.scale_cols2 = D;
+    e.col_scale2 = qk_scale * ATT_LOG2E;
+    if ((st = run_gemm(b.qkv, x16, D * X3, D * X3, B, F, F, e, s, "hubert.qkv"))) return st;
+    if ((st = attention(qkv, o16, B, F, D, s, c->bf16, F_dev))) return st;
+    e = epi();
+    e.add_row = x;
+    e.ld_add_row = D;
+    e.out32 = x;
+    e.ld32 = D;
+    if ((st = run_gemm(b.out, o16, D, D, B, F, F, e, s, "hubert.out"))) return st;
+    if ((st = layernorm_dual(x, b.ln1_g, b.ln1_b, x, x16, (int)rowsF, D, sp, s, c->bf16))) return st;
+    e = epi();
+    e.act = ACT_GELU;
+    e.out16 = h16;
+    e.ld16 = Fd * X3;
+    e.split16 = sp ? Fd : 0;
+    if ((st = run_gemm(b.fc1, x16, D * X3, D * X3, B, F, F, e, s, "hubert.fc1"))) return st;
+    e = epi();
+    e.add_row = x;
+    e.ld_add_row = D;
+    e.out32 = x;
+    e.ld32 = D;
+    if ((st = run_gemm(b.fc2, h16, Fd * X3, Fd * X3, B, F, F, e, s, "hubert.fc2"))) return st;
+    if ((st = layernorm_dual(x, b.ln2_g, b.ln2_b, x, x16, (int)rowsF, D, sp, s, c->bf16))) return st;
+  }
+  e = epi();
+  e.out32 = feats;
+  e.ld32 = c->hFinal;
+  if ((st = run_gemm(c->hfinal, x16, D * X3, D * X3, B, F, F, e, s, "hubert.final_proj"))) return st;
+  return F_dev ? zero_tail_rows(feats, B, F, c->hFinal, F_dev, s) : SVC_OK;
+}
+
+svc_status svc_hubert_encode(svc_ctx* c, const float* wav16, int B, int64_t n, float* feats, void* stream) {
+  CTX_READY(c);
+  return hubert_encode_impl(c, wav16, B, n, nullptr, feats, (hipStream_t)stream);
+}
+
+svc_status svc_hubert_encode_ragged(svc_ctx* c, const float* wav16, int B, int64_t n, const int64_t* utt_samples,
+                                    float* feats, void* stream) {
+  // the arguments and the length table are checked before the context is touched (no HIP call)
+  SVC_REQUIRE(c, "hubert_encode_ragged: null context");
+  SVC_REQUIRE(wav16 && feats, "hubert_encode_ragged: null %s", wav16 ? "feats" : "wav16k");
+  SVC_REQUIRE(B > 0, "hubert_encode_ragged: B=%d", B);
+  for (int b = 0; utt_samples && b < B; ++b)
+    SVC_REQUIRE(utt_samples[b] >= 400 && utt_samples[b] <= n,
+                "hubert_encode_ragged: utterance %d: %lld samples (at least 400 for one frame, batch length %lld)", b,
+                (long long)utt_samples[b], (long long)n);
+  CTX_READY(c);
+  return hubert_encode_impl(c, wav16, B, n, utt_samples, feats, (hipStream_t)stream);
+}
+
+int64_t svc_hubert_frames(int64_t n_samples) { return hubert_len(n_samples, 7); }
+
+int svc_hubert_dims(svc_ctx* c, int* final_dim, int* embed_dim) {
+  SVC_REQUIRE(c && c->has_hubert, "hubert weights not loaded");
+  if (final_dim) *final_dim = c->hFinal;
+  if (embed_dim) *embed_dim = c->hD;
+  return SVC_OK;
+}
+
+// ---------------------------------------------------------------------------- conditioner
+static int condition_impl(svc_ctx* c, const void* content16, const double* f0, const float* energy,
+                          const int32_t* singer, int B, int T, float* cond, f16* cond16, hipStream_t s) {
+  const int rows = B * T;
+  WS_GET(int, im, rows);
+  WS_GET(int, ie, rows);
+  int st;
+  if ((st = bucketize(f0, energy, c->mbins, c->ebins, c->n_bins - 1, im, ie, rows, s))) return st;
+  EpiArgs e = epi();
+  e.kind = EPI_COND;
+  e.idx_m = im;
+  e.idx_l = ie;
+  e.singer = singer;
+  e.emb_m = c->emb_m;
+  e.emb_l = c->emb_l;
+  e.emb_s = c->emb_s;
+  e.ld_emb = c->C;
+  e.out32 = cond;
+  e.ld32 = c->C;
+  e.out16 = cond16;
+  e.ld16 = c->C;
+  return run_gemm(c->content_lin, (const f16*)content16, c->content_dim, c->content_dim, B, T, T, e, s, "cond.content");
+}
+
+svc_status svc_condition_indices(svc_ctx* c, const double* f0, const float* energy, int n, int32_t* melody_idx,
+                                 int32_t* loudness_idx, void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
+  SVC_REQUIRE(n >= 0 && (n == 0 || (f0 && energy && melody_idx && loudness_idx)), "condition_indices: n %d", n);
+  if (n == 0) return SVC_OK;
+  return bucketize(f0, energy, c->mbins, c->ebins, c->n_bins - 1, melody_idx, loudness_idx, n, (hipStream_t)stream);
+}
+
+svc_status svc_condition(svc_ctx* c, const void* content16, const double* f0, const float* energy,
+                         const int32_t* singer, int B, int T, float* cond, void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
+  int st;
+  if ((st = c->ws.reserve(std::max((size_t)B * T * 8 + 4096, c->ws.cap)))) return st;
+  c->ws.reset();
+  return condition_impl(c, content16, f0, energy, singer, B, T, cond, nullptr, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,381 @@
+// The DiffSVC denoiser and its DDPM / PLMS samplers.
+#include <math.h>
+
+#include "engine.h"
+
+// ---------------------------------------------------------------------------- DiffSVC denoiser
+struct DenoiseBufs {
+  f16* cp16;     // [rows][NL*2C] conditioner projections of every layer (hoisted out of the sampler loop)
+  f16* y16;      // [rows][C] next layer input x + diffusion_projection (the high half of the split residual stream)
+  f16* g16;      // [rows][NL*C] gate outputs of every layer (A operand of the skip GEMM)
+  f16* s16;      // [rows][3C] sum(skip) / sqrt(NL) ([hi | lo | hi] split-fp16 with head_split, else [rows][C])
+  f16* u16;      // [rows][3C] relu(skip_projection), same layout
+  f16* lo16;     // [rows][C] low half of the split residual stream: x + dproj = y16 + lo16
+  size_t cp_ls;  // elements between layers of cp16, which is LAYER-major [NL][rows_total][2C]: each layer's gate
+                 // epilogue reads one contiguous block (row-major over all layers put 30 KB between its rows)
+  size_t g_ls;   // elements between layers of g16, also layer-major [NL][rows_total][C]: the gate GEMM writes and the
+                 // residual GEMM reads one contiguous block; the skip GEMM reads the NL blocks as NL "taps" whose row
+                 // shift is the layer stride (tap_mul = rows_total)
+};
+
+
+// tv (device, optional): ragged batches, utterance b has tv[b] valid frames; only the dilated convs look across frames
+// plms (optional): the PLMS update that consumes this eps, launched right after the head
+static int denoise(svc_ctx* c, const DenoiseBufs& bb, const f16* x16, int B, int T, int t, float* eps, hipStream_t s,
+                   const int* tv, const PlmsArgs* plms = nullptr) {
+  const int C = c->C, NL = c->n_layers, rows = B * T;
+  const int ldx16 = (int)round_up(c->n_mel, 8);
+  const float* dp = c->dproj + (size_t)t * NL * C;
+  int st;
+  // Residual stream x in split-fp16 storage (x + dproj_l = y16 + lo16, ~22 significand bits in 4 bytes): the layer's
+  // GEMM operand y16 is its high half, so each residual update moves 10 instead of 12 bytes per element (an f32
+  // residual stream measured 1.1 % slower end to end at the same mel-L1, round 1; removed in round 3).
+  EpiArgs e = epi();
+  e.act = ACT_RELU;
+  e.lo16 = bb.lo16;
+  e.out16 = bb.y16;
+  e.ld16 = C;
+  e.add16 = dp;  // layer 0 diffusion projection
+  if (tuning().res_proj && c->melpre.Wfrag && ldx16 <= 128) {
+    // weight-stationary store stream (res_proj.hip mel_proj), bit-identical to the tiled GEMM
+    prof_site("diffsvc.melpre");
+    if ((st = mel_proj(x16, ldx16, c->melpre.Wfrag, c->melpre.bias, dp, bb.y16, bb.lo16, rows, c->melpre.bf16, s)))
+      return st;
+  } else if ((st = run_gemm(c->melpre, x16, ldx16, c->n_mel, B, T, T, e, s, "diffsvc.melpre"))) {
+    return st;
+  }
+  // the split residual stream's high half, updated in place (y16) by gate + res_proj
+  f16* hi = bb.y16;
+  for (int i = 0; i < NL; ++i) {
+    EpiArgs g = epi();
+    g.kind = EPI_GATE;
+    g.cp = bb.cp16 + (size_t)i * bb.cp_ls;
+    g.ld_cp = 2 * C;
+    g.y16 = bb.g16 + (size_t)i * bb.g_ls;
+    g.ldy16 = C;
+    if ((st = run_gemm(c->dil[i], hi, C, C, B, T, T, g, s, "diffsvc.dilated", tv, 1))) return st;
+    if (i + 1 == NL) break;  // the last layer's residual output is unused (only skips feed the head)
+    // x = (x + residual) / sqrt(2); next input x + diffusion_projection_{i+1}(step):
+    // x_i = (y16 + lo16) - dproj_i, and x_{i+1} + dproj_{i+1} goes back split into y16 / lo16
+    if (tuning().res_proj && C == 384 && c->outres[i].Wfrag && c->outres[i].N == C && c->outres[i].K == C) {
+      // weight-stationary row stream (res_proj.hip), bit-identical to the tiled GEMM below
+      prof_site("diffsvc.outproj");
+      if ((st = res_proj(bb.g16 + (size_t)i * bb.g_ls, c->outres[i].Wfrag, c->outres[i].bias,
+                         dp + (size_t)i * C, dp + (size_t)(i + 1) * C, 1.41421356237309515f, hi, bb.lo16, rows,
+                         c->outres[i].bf16,
+                         tuning().res_proj > 1 ? tuning().res_proj : (tuning().sampler_streams == 1 ? -2 : 0), s)))
+        return st;
+      continue;
+    }
+    EpiArgs r = epi();
+    r.ld_acc = C;
+    r.acc_div = 1.41421356237309515f;
+    r.acc16_hi = hi;
+    r.acc16_lo = bb.lo16;
+    r.acc_sub = dp + (size_t)i * C;
+    r.lo16 = bb.lo16;
+    r.out16 = hi;
+    r.ld16 = C;
+    r.add16 = dp + (size_t)(i + 1) * C;
+    if ((st = run_gemm(c->outres[i], bb.g16 + (size_t)i * bb.g_ls, C, C, B, T, T, r, s, "diffsvc.outproj"))) return st;
+  }
+  // skip = sum_i skip_i (modules/diffsvc.py:311); x = skip / sqrt(len(layers)) (:315)
+  const int H3 = c->head_split ? 3 : 1;  // split-fp16 head operands are [hi | lo | hi] rows
+  e = epi();
+  e.scale_cols = C;
+  e.col_scale = 1.0f / sqrtf((float)NL);
+  e.out16 = bb.s16;
+  e.ld16 = C * H3;
+  e.split16 = H3 == 3 ? C : 0;
+  {
+    PackedGemm sk = c->skip_all;  // K index l * C + k = "tap" l * Cp + k with Cp = C: same packed weights
+    sk.Cp = C;
+    sk.taps = NL;
+    sk.tap_mul = (int)(bb.g_ls / C);
+    sk.tap_add = 0;
+    sk.istride = 1;
+    const int rows_sub = B * T;
+    if ((st = run_gemm(sk, bb.g16, C, C, 1, NL * sk.tap_mul, rows_sub, e, s, "diffsvc.skipsum"))) return st;
+  }
+  // relu(skip_projection) and output_projection in one launch: u never reaches HBM (diff_head.hip)
+  if (tuning().diff_head && H3 == 3 && C == 384 && c->skipproj.N == C && c->skipproj.Npad >= C &&
+      c->skipproj.K == 3 * C && c->skipproj.Kpad == 3 * C && c->outproj.K == 3 * C && c->outproj.Kpad == 3 * C &&
+      c->outproj.Npad >= 128 && c->outproj.N <= 128 && c->n_mel % 4 == 0) {
+    if ((st = diff_head(bb.s16, c->skipproj.W, c->skipproj.bias, C, 3 * C, c->outproj.W, c->outproj.bias,
+                        c->outproj.N, 3 * C, c->outproj.Npad, eps, c->n_mel, (int)rows, zero_page(), s,
+                        c->skipproj.bf16)))
+      return st;
+    return plms ? plms_update(*plms, rows, c->n_mel, s) : SVC_OK;
+  }
+  e = epi();
+  e.act = ACT_RELU;
+  e.out16 = bb.u16;
+  e.ld16 = C * H3;
+  e.split16 = H3 == 3 ? C : 0;
+  if ((st = run_gemm(c->skipproj, bb.s16, C * H3, C * H3, B, T, T, e, s, "diffsvc.skipproj"))) return st;
+  e = epi();
+  e.out32 = eps;
+  e.ld32 = c->n_mel;
+  if ((st = run_gemm(c->outproj, bb.u16, C * H3, C * H3, B, T, T, e, s, "diffsvc.eps_out"))) return st;
+  return plms ? plms_update(*plms, rows, c->n_mel, s) : SVC_OK;
+}
+
+static int alloc_denoise(svc_ctx* c, int B, int T, DenoiseBufs& bb) {
+  const size_t rows = (size_t)B * T, C = c->C;
+  WS_GET(f16, cp16, rows * c->n_layers * 2 * C);
+  WS_GET(f16, y16, rows * C);
+  WS_GET(f16, g16, rows * c->n_layers * C);
+  WS_GET(f16, s16, rows * C * 3);  // [hi | lo | hi] when head_split
+  WS_GET(f16, u16, rows * C * 3);
+  WS_GET(f16, lo16, rows * C);
+  bb = DenoiseBufs{cp16, y16, g16, s16, u16, lo16, rows * 2 * C, rows * C};
+  return SVC_OK;
+}
+
+static size_t denoise_bytes(svc_ctx* c, int B, int T) {
+  const size_t rows = (size_t)B * T, C = c->C;
+  return rows * c->n_layers * 2 * C * 2 + rows * c->n_layers * C * 2 + rows * C * 2 * 9 + 26 * 4096;
+}
+
+static int project_cond(svc_ctx* c, const float* cond, int B, int T, const DenoiseBufs& bb, hipStream_t s) {
+  const int rows = B * T, C = c->C;
+  WS_GET(f16, cond16, (size_t)rows * 3 * C);
+  int st;
+  if ((st = f32_to_f16x3(cond, C, cond16, rows, C, s, c->bf16))) return st;  // [hi | lo | hi] split-fp16 operand
+  // the projections of all layers as ONE GEMM over the packed weights (N = NL x 2C), each layer's 2C columns written
+  // to its layer-major cp block (EpiArgs col_block): 20 launches of 470 tiles (1.8 rounds of workgroups each) became
+  // one launch of 9 400 (round 5)
+  EpiArgs e = epi();
+  e.out16 = bb.cp16;
+  e.ld16 = 2 * C;
+  e.col_block = 2 * C;
+  e.col_block_stride = (int64_t)bb.cp_ls;
+  if ((st = run_gemm(c->cp_all, cond16, 3 * C, 3 * C, B, T, T, e, s, "diffsvc.condproj"))) return st;
+  return SVC_OK;
+}
+
+namespace svc {
+
+// ragged batches: validate the per-utterance frame counts (host) and stage them to the device through `ring`
+int stage_frames(StageRing& ring, const int32_t* frames, int B, int T, hipStream_t s, const int** dev_out) {
+  *dev_out = nullptr;
+  if (!frames) return SVC_OK;
+  for (int b = 0; b < B; ++b)
+    SVC_REQUIRE(frames[b] >= 1 && frames[b] <= T, "utterance %d: %d frames (batch length %d)", b, frames[b], T);
+  void* dev = nullptr;
+  int st = ring.put(frames, (size_t)B * sizeof(int32_t), s, &dev);
+  *dev_out = reinterpret_cast<const int*>(dev);
+  return st;
+}
+
+}  // namespace svc
+
+static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* tv, int mode, int interval,
+                       const float* x_T, const float* noise, uint64_t seed, const int32_t* utt_ids, float* x0,
+                       hipStream_t stream) {
+  SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
+  SVC_REQUIRE(mode == SVC_MODE_DDPM || (mode == SVC_MODE_PLMS && interval >= 1), "sample: mode %d interval %d", mode,
+              interval);
+  SVC_REQUIRE(x_T || utt_ids, "sample: need x_T or utt_ids for device noise");
+  // DDPM draws step noise on the device unless `noise` is given; that noise is keyed by utterance id
+  SVC_REQUIRE(mode != SVC_MODE_DDPM || noise || utt_ids, "sample: DDPM without `noise` needs utt_ids");
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = B * T, nm = c->n_mel, ld16 = (int)round_up(nm, 8);
+  int st;
+  const size_t extra = (size_t)rows * (ld16 * 2 * 2 + nm * 4 * 8 + c->C * 6) + 32 * 4096;
+  if ((st = c->ws.reserve(std::max(denoise_bytes(c, B, T) + extra, c->ws.cap)))) return st;
+  c->ws.reset();
+  DenoiseBufs bb;
+  if ((st = alloc_denoise(c, B, T, bb))) return st;
+  if ((st = project_cond(c, cond, B, T, bb, s))) return st;
+  float* x = x0;  // the sampler state lives in the output buffer
+  WS_GET(f16, x16, (size_t)rows * ld16);
+  SVC_HIP_CHECK(hipMemsetAsync(x16, 0, (size_t)rows * ld16 * sizeof(f16), s));  // zero pad channels
+  if (x_T) {
+    SVC_HIP_CHECK(hipMemcpyAsync(x, x_T, (size_t)rows * nm * 4, hipMemcpyDeviceToDevice, s));
+    if ((st = f32_to_f16(x, nm, x16, ld16, rows, nm, ld16, s, c->bf16))) return st;
+  } else {
+    if ((st = init_noise(x, x16, ld16, B, T, nm, seed, utt_ids, 1.0f / 1.2f, s, c->bf16))) return st;
+  }
+  WS_GET(float, eps, (size_t)rows * nm);
+  float* hist[5];
+  for (int k = 0; k < 5; ++k) {
+    WS_GET(float, hb, (size_t)rows * nm);
+    hist[k] = hb;
+  }
+  WS_GET(float, xp, (size_t)rows * nm);
+  WS_GET(f16, xp16, (size_t)rows * ld16);
+  SVC_HIP_CHECK(hipMemsetAsync(xp16, 0, (size_t)rows * ld16 * sizeof(f16), s));
+
+  // Utterance-aligned sub-batches on their own streams, issued kernel by kernel in alternation: their
+  // launches overlap on the GPU, so one sub-batch's epilogue / prologue phases (HBM-bound, ~40 % of a
+  // denoiser GEMM launch at this size) run beside the other's MFMA phases. Utterances are independent,
+  // so results are identical to a single stream. Default 2 (round-2 final code, alternating A/B on two boxes:
+  // +0.9 % over 3, 4: -15 %; profiles/r02zf_streams_ab.txt); sampler_streams = 1 disables the split.
+  SubBatches sb;
+  if ((st = sb.fork(c, tuning().sampler_streams, B, s))) return st;
+  const int S = sb.n;
+  struct Sub {
+    int B, b0;
+    size_t r0;
+  } sub[kMaxSubStreams];
+  for (int h = 0; h < S; ++h) {
+    sub[h].b0 = sb.b0(h);
+    sub[h].B = sb.b0(h + 1) - sub[h].b0;
+    sub[h].r0 = (size_t)sub[h].b0 * T;
+  }
+  auto sub_bufs = [&](const Sub& u) {
+    const size_t r = u.r0;
+    const int C = c->C;
+    return DenoiseBufs{bb.cp16 + r * 2 * C, bb.y16 + r * C, bb.g16 + r * C, bb.s16 + r * 3 * C, bb.u16 + r * 3 * C,
+                       bb.lo16 + r * C, bb.cp_ls, bb.g_ls};
+  };
+
+  if (mode == SVC_MODE_DDPM) {
+    for (int i = c->steps - 1; i >= 0; --i) {
+      for (int h = 0; h < S; ++h) {
+        const Sub& u = sub[h];
+        const size_t r = u.r0;
+        const hipStream_t us = sb.stream(h);
+        if ((st = denoise(c, sub_bufs(u), x16 + r * ld16, u.B, T, i, eps + r * nm, us, tv ? tv + u.b0 : nullptr)))
+          return st;
+        DdpmArgs a{};
+        a.sra = c->sra[i];
+        a.srm1 = c->srm1[i];
+        a.c1 = c->pc1[i];
+        a.c2 = c->pc2[i];
+        a.sigma = i > 0 ? expf(0.5f * c->plogvar[i]) : 0.0f;
+        a.z = noise ? noise + (size_t)(c->steps - 1 - i) * rows * nm + r * nm : nullptr;
+        a.seed = seed;
+        a.utt_ids = utt_ids ? utt_ids + u.b0 : nullptr;
+        a.step = i;
+        a.bf16 = c->bf16;
+        if ((st = ddpm_update(x + r * nm, eps + r * nm, x16 + r * ld16, ld16, u.B, T, nm, a, us))) return st;
+      }
+    }
+    return sb.join();
+  }
+  // PLMS: history ring of 4 epsilons + the first step's predictor buffers (the ring position is shared)
+  int nh = 0, head = 0;  // hist slots: newest at hist[(head - 1) mod 5]
+  const std::vector<float>& ac = c->alphas_cumprod_f32;
+  for (int i = ((c->steps - 1) / interval) * interval; i >= 0; i -= interval) {
+    const int tp = i - interval > 0 ? i - interval : 0;
+    // get_x_pred coefficients in f32 exactly as the reference's tensor ops (:96-113)
+    const float a_t = ac[i], a_prev = ac[tp];
+    const float a_t_sq = sqrtf(a_t), a_prev_sq = sqrtf(a_prev);
+    const float A = 1.0f / (a_t_sq * (a_t_sq + a_prev_sq));
+    const float Bc = 1.0f / (a_t_sq * (sqrtf((1.0f - a_prev) * a_t) + sqrtf((1.0f - a_t) * a_prev)));
+    const float d = a_prev - a_t;
+    for (int h = 0; h < S; ++h) {
+      const Sub& u = sub[h];
+      const size_t r = u.r0;
+      const hipStream_t us = sb.stream(h);
+      const DenoiseBufs ub = sub_bufs(u);
+      float* ecur = hist[head] + r * nm;
+      PlmsArgs p{};
+      p.bf16 = c->bf16;
+      p.d = d;
+      p.A = A;
+      p.Bc = Bc;
+      p.xin = x + r * nm;
+      p.xout = x + r * nm;
+      p.x16 = x16 + r * ld16;
+      p.ld16 = ld16;
+      auto H = [&](int back) { return hist[((head - back) % 5 + 5) % 5] + r * nm; };
+      // each update runs in (or right after) the denoise whose eps it consumes (denoise's plms argument)
+      if (nh == 0) {
+        PlmsArgs q = p;
+        q.e[0] = ecur;
+        q.c[0] = 1.0f;
+        q.ne = 1;
+        q.div = 1.0f;
+        q.xout = xp + r * nm;
+        q.x16 = xp16 + r * ld16;
+        if ((st = denoise(c, ub, x16 + r * ld16, u.B, T, i, ecur, us, tv ? tv + u.b0 : nullptr, &q)))
+          return st;
+        float* eprev = hist[(head + 1) % 5] + r * nm;
+        p.e[0] = ecur;
+        p.e[1] = eprev;
+        p.c[0] = 1.0f;
+        p.c[1] = 1.0f;
+        p.ne = 2;
+        p.div = 2.0f;
+        if ((st = denoise(c, ub, xp16 + r * ld16, u.B, T, tp, eprev, us, tv ? tv + u.b0 : nullptr, &p)))
+          return st;
+        continue;
+      } else if (nh == 1) {
+        p.e[0] = ecur;
+        p.e[1] = H(1);
+        p.c[0] = 3.0f;
+        p.c[1] = -1.0f;
+        p.ne = 2;
+        p.div = 2.0f;
+      } else if (nh == 2) {
+        p.e[0] = ecur;
+        p.e[1] = H(1);
+        p.e[2] = H(2);
+        p.c[0] = 23.0f;
+        p.c[1] = -16.0f;
+        p.c[2] = 5.0f;
+        p.ne = 3;
+        p.div = 12.0f;
+      } else {
+        p.e[0] = ecur;
+        p.e[1] = H(1);
+        p.e[2] = H(2);
+        p.e[3] = H(3);
+        p.c[0] = 55.0f;
+        p.c[1] = -59.0f;
+        p.c[2] = 37.0f;
+        p.c[3] = -9.0f;
+        p.ne = 4;
+        p.div = 24.0f;
+      }
+      if ((st = denoise(c, ub, x16 + r * ld16, u.B, T, i, ecur, us, tv ? tv + u.b0 : nullptr, &p)))
+        return st;
+    }
+    head = (head + 1) % 5;
+    nh = nh < 4 ? nh + 1 : 4;
+  }
+  return sb.join();
+}
+
+extern "C" {
+
+svc_status svc_diffsvc_eps(svc_ctx* c, const float* cond, const float* x, int B, int T, const int32_t* frames, int t,
+                           float* eps, void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
+  SVC_REQUIRE(t >= 0 && t < c->steps, "eps: t=%d", t);
+  hipStream_t s = (hipStream_t)stream;
+  const int* tv;
+  RingRetire retire_(c->lens_main, s);
+  if (int st0 = stage_frames(c->lens_main, frames, B, T, s, &tv)) return st0;
+  const int rows = B * T, ld16 = (int)round_up(c->n_mel, 8);
+  int st;
+  if ((st = c->ws.reserve(std::max(denoise_bytes(c, B, T) + (size_t)rows * (ld16 * 2 + c->C * 6) + 8192, c->ws.cap))))
+    return st;
+  c->ws.reset();
+  DenoiseBufs bb;
+  if ((st = alloc_denoise(c, B, T, bb))) return st;
+  if ((st = project_cond(c, cond, B, T, bb, s))) return st;
+  WS_GET(f16, x16, (size_t)rows * ld16);
+  if ((st = f32_to_f16(x, c->n_mel, x16, ld16, rows, c->n_mel, ld16, s, c->bf16))) return st;
+  if ((st = denoise(c, bb, x16, B, T, t, eps, s, tv))) return st;
+  return tv ? zero_tail_rows(eps, B, T, c->n_mel, tv, s) : SVC_OK;
+}
+
+svc_status svc_diffsvc_sample(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames, int mode,
+                              int interval, const float* x_T, const float* noise, uint64_t seed,
+                              const int32_t* utt_ids, float* x0, void* stream) {
+  CTX_READY(c);
+  hipStream_t s = (hipStream_t)stream;
+  const int* tv;
+  RingRetire retire_(c->lens_main, s);
+  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
+  if (st || (st = sample_impl(c, cond, B, T, tv, mode, interval, x_T, noise, seed, utt_ids, x0, s))) return st;
+  // frames past an utterance's end hold no sample: zero them
+  return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+}
+
+}  // extern "C"

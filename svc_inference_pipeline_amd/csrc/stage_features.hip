@@ -1,0 +1,197 @@
+// The waveform-side stages: mel + energy, the F0 front ends, 16-bit PCM output and wav payload decoding.
+#include "engine.h"
+
+extern "C" {
+
+// ---------------------------------------------------------------------------- mel + energy
+// mel frames of an n-sample clip (utils/mel.py:148-167: reflect pad (n_fft - hop) / 2 each side, center=False)
+static int64_t mel_frames_of(const svc_ctx* c, int64_t n) {
+  const int pad = (c->n_fft - c->hop) / 2;
+  return (n + 2 * pad - c->n_fft) / c->hop + 1;
+}
+
+// ragged batches: validate the per-utterance sample counts (host) and stage them with their mel frame counts
+// (int64 n[B] then int T[B]) to the device through `ring`
+static int stage_samples(svc_ctx* c, StageRing& ring, const int64_t* n_samples, int B, int64_t n, hipStream_t s,
+                         const int64_t** nb_dev, const int** Tb_dev, std::vector<int>* Tb_host) {
+  *nb_dev = nullptr;
+  *Tb_dev = nullptr;
+  if (!n_samples) return SVC_OK;
+  const int pad = (c->n_fft - c->hop) / 2;
+  std::vector<char> buf((size_t)B * (8 + 4));
+  int64_t* nv = reinterpret_cast<int64_t*>(buf.data());
+  int* tv = reinterpret_cast<int*>(buf.data() + (size_t)B * 8);
+  Tb_host->resize(B);
+  for (int b = 0; b < B; ++b) {
+    SVC_REQUIRE(n_samples[b] > pad && n_samples[b] <= n, "utterance %d: %lld samples (batch length %lld)", b,
+                (long long)n_samples[b], (long long)n);
+    nv[b] = n_samples[b];
+    tv[b] = (int)mel_frames_of(c, n_samples[b]);
+    (*Tb_host)[b] = tv[b];
+  }
+  void* dev = nullptr;
+  int st = ring.put(buf.data(), buf.size(), s, &dev);
+  if (st) return st;
+  *nb_dev = reinterpret_cast<const int64_t*>(dev);
+  *Tb_dev = reinterpret_cast<const int*>(reinterpret_cast<char*>(dev) + (size_t)B * 8);
+  return SVC_OK;
+}
+
+svc_status svc_mel_energy(svc_ctx* c, const float* wav, int B, int64_t n, const int64_t* n_samples, float* mel,
+                          float* energy, void* stream) {
+  CTX_READY(c);
+  hipStream_t s = (hipStream_t)stream;
+  const int pad = (c->n_fft - c->hop) / 2;
+  const int64_t T64 = mel_frames_of(c, n);
+  SVC_REQUIRE(B > 0 && n > pad && T64 > 0 && T64 < (1 << 30), "mel_energy: n=%lld", (long long)n);
+  const int T = (int)T64, nb = c->n_fft / 2 + 1;
+  const int64_t* nb_dev;
+  const int* Tb_dev;
+  std::vector<int> Tb_host;
+  RingRetire retire_(c->lens_feat, s);
+  int st0 = stage_samples(c, c->lens_feat, n_samples, B, n, s, &nb_dev, &Tb_dev, &Tb_host);
+  if (st0) return st0;
+  int st;
+  DftArgs a{};
+  a.wav = wav;
+  a.wav_stride = n;
+  a.n_valid = n;
+  a.n_logical = n;
+  a.n_fft = c->n_fft;
+  a.hop = c->hop;
+  a.pad = pad;
+  a.n_frames = T;
+  a.nbins = nb;
+  a.window = c->win_mel;
+  a.twiddle = reinterpret_cast<const double2*>(c->tw24);
+  a.mode = 0;
+  a.fb = c->fb24;
+  a.band = c->band24;
+  a.fb_len = c->fb24_len;
+  a.n_mels = c->n_mels;
+  a.out = mel;
+  a.energy = energy;
+  a.nb = nb_dev;
+  a.Tb = Tb_dev;
+  if ((st = dft_mel(a, B, s))) return st;
+  if (Tb_dev && ((st = zero_tail_rows(mel, B, T, c->n_mels, Tb_dev, s)) || (st = zero_tail_rows(energy, B, T, 1, Tb_dev, s))))
+    return st;
+  return SVC_OK;
+}
+
+// ---------------------------------------------------------------------------- F0
+svc_status svc_f0_ac(svc_ctx* c, const float* wav, int B, int64_t n, const int64_t* n_samples, int T, double* f0,
+                     void* stream) {
+  CTX_READY(c);
+  const double ts = (double)c->hop / c->fs;
+  size_t need = f0_workspace_bytes(B, n, c->fs, ts, c->f0_min);
+  int st;
+  if ((st = c->auxws.reserve(std::max(need + 4096, c->auxws.cap)))) return st;
+  std::vector<int> Tb;
+  if (n_samples) {
+    Tb.resize(B);
+    for (int b = 0; b < B; ++b) Tb[b] = (int)mel_frames_of(c, n_samples[b]);
+  }
+  const double key[2] = {(double)c->fs, c->f0_min};
+  double* f0_tab = c->f0_tabs.find(key, 2);
+  if (!f0_tab) {
+    std::vector<double> tab(f0_table_doubles(c->fs, c->f0_min));
+    if ((st = f0_tables(c->fs, c->f0_min, tab.data()))) return st;
+    void* p = nullptr;
+    SVC_HIP_CHECK(hipMalloc(&p, tab.size() * 8));
+    const hipError_t me = hipMemcpy(p, tab.data(), tab.size() * 8, hipMemcpyHostToDevice);
+    if (me != hipSuccess) (void)hipFree(p);
+    SVC_HIP_CHECK(me);
+    f0_tab = reinterpret_cast<double*>(p);
+    if ((st = c->f0_tabs.insert(key, 2, f0_tab))) return st;
+  }
+  RingRetire retire_(c->lens_feat, (hipStream_t)stream);
+  return f0_praat_ac(wav, B, n, c->fs, ts, c->f0_min, c->f0_max, 0.6, T, f0, c->auxws.base, c->auxws.cap, f0_tab,
+                     (hipStream_t)stream, n_samples, n_samples ? Tb.data() : nullptr, &c->lens_feat);
+}
+
+svc_status svc_f0_pyin(svc_ctx* c, const float* wav, int B, int64_t n, const int64_t* n_samples, double fs,
+                       int win_length, int hop_length, double f0_min, double f0_max, int T, double* f0, void* stream) {
+  SVC_REQUIRE(c, "null context");
+  TuningScope tuning_scope_(&c->tune);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  const int FL = 2048;  // librosa.pyin frame_length default (utils/f0.py:107 leaves it unset)
+  const size_t nt = pyin_table_doubles(fs, f0_min, f0_max, FL, win_length, hop_length);
+  if (!nt) return SVC_ERR_INVALID;  // (pyin_plan set the error)
+  SVC_REQUIRE(B > 0 && n > 0 && T > 0, "pyin: B=%d n=%lld T=%d", B, (long long)n, T);
+  const size_t need = pyin_workspace_bytes(B, T, fs, f0_min, f0_max, FL, win_length, hop_length);
+  int st;
+  if ((st = c->auxws.reserve(std::max(need + 4096, c->auxws.cap)))) return st;
+  // the tables depend only on (fs, f0_min, f0_max, win, hop): built and uploaded once per parameter set
+  const double key[5] = {fs, f0_min, f0_max, (double)win_length, (double)hop_length};
+  double* pyin_tab = c->pyin_tabs.find(key, 5);
+  if (!pyin_tab) {
+    std::vector<double> tab(nt);
+    if ((st = pyin_tables(fs, f0_min, f0_max, FL, win_length, hop_length, tab.data()))) return st;
+    void* p = nullptr;
+    SVC_HIP_CHECK(hipMalloc(&p, nt * 8));
+    const hipError_t me = hipMemcpy(p, tab.data(), nt * 8, hipMemcpyHostToDevice);
+    if (me != hipSuccess) (void)hipFree(p);
+    SVC_HIP_CHECK(me);
+    pyin_tab = reinterpret_cast<double*>(p);
+    if ((st = c->pyin_tabs.insert(key, 5, pyin_tab))) return st;
+  }
+  // only the per-call lengths are staged (the ring retires its last slot)
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_feat, s);
+  const int64_t* nb_dev = nullptr;
+  if (n_samples) {
+    void* dev = nullptr;
+    if ((st = c->lens_feat.put(n_samples, (size_t)B * 8, s, &dev))) return st;
+    nb_dev = reinterpret_cast<const int64_t*>(dev);
+  }
+  return f0_pyin(wav, B, n, nb_dev, n_samples, fs, f0_min, f0_max, FL, win_length, hop_length, T, f0, c->auxws.base,
+                 c->auxws.cap, pyin_tab, s);
+}
+
+svc_status svc_pitch_shift(svc_ctx* c, double* f0, int B, int T, double target_median, void* stream) {
+  SVC_REQUIRE(c && f0 && B > 0 && T > 0, "pitch_shift: bad args");
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  return pitch_shift(f0, B, T, target_median, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------- 16-bit PCM (A16)
+svc_status svc_pcm16(svc_ctx* c, const float* wav, int B, int64_t S, const int64_t* utt_samples, int fs,
+                     int add_silence, int turn_up, double volume_peak, void* pcm, float* peak_out, void* stream) {
+  SVC_REQUIRE(c, "pcm16: null context");
+  SVC_REQUIRE(wav && pcm, "pcm16: null %s", wav ? "pcm" : "wav");
+  SVC_REQUIRE(B >= 1 && S >= 1, "pcm16: B=%d S=%lld", B, (long long)S);
+  SVC_REQUIRE(fs >= 1, "pcm16: fs=%d", fs);
+  SVC_REQUIRE(!turn_up || volume_peak > 0.0, "pcm16: volume_peak %g (must be positive with turn_up)", volume_peak);
+  // one staged table (pcm16.hip): int64 n[B], then the peak scratch, whose zeros the same stream-ordered copy writes
+  std::vector<char> buf(pcm16_table_bytes(B), 0);
+  int64_t* nv = reinterpret_cast<int64_t*>(buf.data());
+  int64_t max_nb = 0;
+  for (int b = 0; b < B; ++b) {
+    nv[b] = utt_samples ? utt_samples[b] : S;
+    SVC_REQUIRE(nv[b] >= 0 && nv[b] <= S, "pcm16: utterance %d: %lld samples (batch length %lld)", b, (long long)nv[b],
+                (long long)S);
+    max_nb = std::max(max_nb, nv[b]);
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int sil = add_silence ? fs / 20 : 0;
+  RingRetire retire_(c->lens_pcm, s);
+  void* dev = nullptr;
+  if (int st = c->lens_pcm.put(buf.data(), buf.size(), s, &dev)) return st;
+  return pcm16(wav, B, S, dev, max_nb, sil, S + 2 * (int64_t)sil, turn_up ? 1 : 0, volume_peak,
+               reinterpret_cast<int16_t*>(pcm), peak_out, (turn_up || peak_out) ? 1 : 0, s);
+}
+
+// ---------------------------------------------------------------------------- wav payloads -> the input batches (A1)
+svc_status svc_load_pcm(svc_ctx* c, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+                        const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,
+                        int64_t S_src, float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info,
+                        void* stream) {
+  SVC_REQUIRE(c, "load_pcm: null context");
+  // the context is read only once the arguments have passed (load_pcm.hip checks them before any HIP call)
+  return load_pcm(&c->lens_load, &c->device, raw, B, byte_off, n_frames, format, channels, sr_in, sr_src, S_src, y_src,
+                  sr_mono, S_mono, y_mono, info, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -65,7 +65,7 @@ def noise_block(seed, utt_ids, step, T, C):
 
 # ------------------------------------------------------------------ schedule coefficients
 def schedule():
-    """float64 betas of the committed configuration -> dict of the float32 tables the engine keeps (engine.hip
+    """float64 betas of the committed configuration -> dict of the float32 tables the engine keeps (finalize.hip build_mapper, run by
     svc_ctx_finalize; modules/diffsvcrepo_inference.py:163-197)."""
     from svc_inference_pipeline_amd import config as C
     betas = C.noise_schedule(C.load_config().mapper)
