@@ -20,6 +20,8 @@
  *   svc_load_pcm        <- utils/audio.py:10-55 load_audio_torch + utils/whisper_extractor/audio.py:22-49 load_audio
  *                          (sample decode, normalisation, mono mix and both resamplings of a ragged batch of wav
  *                          payloads; the RIFF header is parsed on the host)
+ *   svc_load_pcm_ex     <- the same, plus utils/hubert.py:137-143 librosa.load(path, sr=16000): the float 16 kHz mono
+ *                          rows HuBERT / ContentVec reads, from the launch that writes Whisper's rows
  *   svc_pcm16           <- utils/util.py:20-37 save_audio (peak normalisation, silence, 16-bit samples; the file
  *                          itself is written on the host)
  *
@@ -265,6 +267,27 @@ svc_status svc_load_pcm(svc_ctx* ctx, const void* raw, int B, const int64_t* byt
                         const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,
                         int64_t S_src, float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info,
                         void* stream);
+
+/* A1 with HuBERT / ContentVec's input: svc_load_pcm with a third output, the float mono rows that replace
+   utils/hubert.py:137-143's librosa.load(path, sr=16000) for wav input. svc_load_pcm is the y_mono_float == NULL case
+   (the same results bit for bit, the same launches).
+   y_mono_float f32 [B][S_mono] (or NULL): row b = the mean over the channels exactly as y_mono takes it (f64, numpy's
+   order) as float; where sr_in[b] != sr_mono, svc_resample's filter output (float)acc WITHOUT the int16 rounding (the
+   value y_mono's sample is rounded from); where sr_in[b] == sr_mono, the float means themselves, unfiltered
+   (librosa.load does not resample at the native rate; y_mono's row of the same utterance still goes through the
+   up = down = 1 filter). Same length as y_mono's row, svc_resample_len(n_frames[b], sr_in[b], sr_mono), zeros after it
+   to S_mono. Row b is bit for bit audio.load_contentvec_audio of that file alone. The row is not examined for
+   non-finite samples; info is as svc_load_pcm writes it.
+   Both mono rows come from ONE launch (one decode of the input into LDS, one pass over the taps, two stores), so a call
+   stays at three launches at most (peak, source, mono) whichever rows are asked for. Any of the three outputs may be
+   NULL, not all three; a row computed with the others present is bit-identical to the same row computed alone. With
+   y_mono_float alone, rows already at sr_mono need no filter plan.
+   SVC_ERR_INVALID before any HIP call as svc_load_pcm, with: all three outputs NULL; sr_mono / S_mono < 1 or S_mono
+   shorter than the longest mono row when either mono output is given. */
+svc_status svc_load_pcm_ex(svc_ctx* ctx, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+                           const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,
+                           int64_t S_src, float* y_src, int sr_mono, int64_t S_mono, float* y_mono,
+                           float* y_mono_float, int32_t* info, void* stream);
 
 /* host-only: samples per output row for a batch whose longest utterance has n_samples:
    n_samples + 2 * (add_silence ? fs / 20 : 0); -1 for n_samples < 0 or fs < 1 */

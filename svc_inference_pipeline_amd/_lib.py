@@ -48,6 +48,8 @@ PROTOTYPES = {
     "svc_bigvgan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svc_load_pcm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
                              c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "svc_load_pcm_ex": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svc_pcm16_len": (c_int64, [c_int64, c_int, c_int]),
     "svc_pcm16": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
                           c_void_p, c_void_p]),

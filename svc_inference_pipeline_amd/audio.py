@@ -3,9 +3,10 @@
     load_audio_torch(wave_file, fs)   utils/audio.py:10-55            -> load_audio (+ resample on the GPU)
     load_audio(file, sr=16000)        utils/whisper_extractor/audio.py:22-49 (ffmpeg s16le decode)
                                                                       -> load_whisper_audio
+    librosa.load(path, sr=16000)      utils/hubert.py:137-143          -> load_contentvec_audio
     save_audio(path, waveform, fs)    utils/util.py:20-37              -> save_audio
-    both loaders for a batch of files                                 -> load_batch (parse_wav on the host, one
-                                                                         svc_load_pcm call on the GPU)
+    the loaders for a batch of files                                  -> load_batch (parse_wav on the host, one
+                                                                         svc_load_pcm / svc_load_pcm_ex call on the GPU)
 
 The reference reads wavs with soundfile, resamples with librosa (soxr) and decodes Whisper's 16 kHz input with
 an ffmpeg subprocess; none of the three is in this image. Here a RIFF/WAVE reader gives soundfile's float
@@ -164,7 +165,20 @@ def load_whisper_audio(path, sr=WHISPER_SR, device="cuda"):
     return resample(mono, sr_in, sr, device=device, quantize16=True)
 
 
-def load_batch(sources, fs, engine, on_error="raise"):
+def load_contentvec_audio(path, sr=WHISPER_SR, device="cuda"):
+    """utils/hubert.py:137-143 librosa.load(path, sr=16000) for a wav: mono down-mix as float32, resampled to `sr`
+    without quantisation, and not resampled at all when the file already is at `sr` (librosa.load's rule).
+    Unpinned against librosa in two places: librosa's to_mono takes the mean of the float32 samples (equal to the
+    float64 mean taken here, then rounded, for 1 and 2 channels; for more than 2 channels it may differ in the last
+    bit), and librosa resamples with soxr where this is svc_resample's Kaiser polyphase filter."""
+    audio, sr_in = read_wav(path)
+    mono = audio.mean(axis=1).astype(np.float32)
+    if sr_in == sr:
+        return torch.as_tensor(mono, device=device)
+    return resample(mono, sr_in, sr, device=device, quantize16=False)
+
+
+def load_batch(sources, fs, engine, on_error="raise", float16k=False):
     """load_audio and load_whisper_audio for a batch of wav files (paths, bytes or memoryviews; or WavInfo already
     parsed) in ONE device stage: headers on the host, then one upload and one svc_load_pcm call
     (SVCEngine.load_pcm) -> (wavs24, wavs16), lists of per-utterance row views of the two padded batches (what
@@ -172,7 +186,9 @@ def load_batch(sources, fs, engine, on_error="raise"):
     AudioError naming the source: a file of <= 2 frames (load_audio), or one with non-finite samples (where load_audio
     returns None and infer.py raises). on_error="return": nothing is raised for a bad file; the result is
     (wavs24, wavs16, errors) with None for it in both lists and its exception in errors (a dict by position); the other
-    files are decoded as usual."""
+    files are decoded as usual.
+    float16k=True: load_contentvec_audio as well, from the same call (svc_load_pcm_ex) -> (wavs24, wavs16,
+    wavs16_float), or (wavs24, wavs16, wavs16_float, errors); a failed file is None in the third list too."""
     infos, errors = [], {}
     for i, src in enumerate(sources):
         try:
@@ -187,9 +203,12 @@ def load_batch(sources, fs, engine, on_error="raise"):
             if on_error == "raise":
                 raise
             errors[i] = exc
-    w24, w16 = [None] * len(sources), [None] * len(sources)
+    w24, w16, w16f = [None] * len(sources), [None] * len(sources), [None] * len(sources)
     if infos:
-        y24, y16, n24, n16, flags = engine.load_pcm([info for _, info in infos], fs)
+        if float16k:
+            y24, y16, n24, n16, flags, y16f = engine.load_pcm([info for _, info in infos], fs, float_mono=True)
+        else:
+            y24, y16, n24, n16, flags = engine.load_pcm([info for _, info in infos], fs)
         # integer samples cannot be non-finite: the flags are fetched only when some file holds floats
         bits = flags.cpu().tolist() if any(info.format >= 4 for _, info in infos) else [0] * len(infos)
         for j, (i, info) in enumerate(infos):
@@ -197,11 +216,14 @@ def load_batch(sources, fs, engine, on_error="raise"):
                 errors[i] = AudioError(f"{info.name}: non-finite samples")
                 continue
             w24[i], w16[i] = y24[j, :n24[j]], y16[j, :n16[j]]
+            if float16k:
+                w16f[i] = y16f[j, :n16[j]]
+    out = (w24, w16, w16f) if float16k else (w24, w16)
     if on_error == "raise":
         if errors:
             raise errors[min(errors)]
-        return w24, w16
-    return w24, w16, errors
+        return out
+    return out + (errors,)
 
 
 def to_pcm16(waveform, fs, add_silence=True, turn_up=True, volume_peak=0.9):

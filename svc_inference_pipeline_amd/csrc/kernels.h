@@ -89,7 +89,8 @@ int pcm16(const float* wav, int B, int64_t S, void* table, int64_t max_nb, int s
           double volume_peak, int16_t* pcm, float* peak_out, int need_peak, hipStream_t s);
 int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
              const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
-             float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info, hipStream_t s);
+             float* y_src, int sr_mono, int64_t S_mono, float* y_mono, float* y_mono_float, bool ex, int32_t* info,
+             hipStream_t s);
 // resample.hip: the cached plan of a rate pair (design_plan's integers) and its taps once more in phase-major order on
 // the device, hpm[k0 * per_phase + r] = h[k0 + up * r] (per_phase = (taps - 1) / up + 1); 0, or -1 when the upload failed
 int get_plan_pm(int sr_in, int sr_out, const double** hpm, int* up, int* down, int* pre_remove, int* taps,

@@ -1,8 +1,10 @@
 // A1: the input end of infer.py on the device. The data-chunk payloads of B wav files (one byte buffer, any byte
 // offsets) -> the two ragged batches the pipeline consumes: the source waveform at the model rate
 // (utils/audio.py:10-55 load_audio_torch -> audio.load_audio) and Whisper's 16 kHz mono int16-grid copy
-// (utils/whisper_extractor/audio.py:22-49 load_audio -> audio.load_whisper_audio). At most three launches per call,
-// whatever B is: the channel-0 peak (only when some utterance holds float samples), the source rows, the mono rows.
+// (utils/whisper_extractor/audio.py:22-49 load_audio -> audio.load_whisper_audio), and with svc_load_pcm_ex HuBERT /
+// ContentVec's float mono copy at the same rate (utils/hubert.py:137-143 librosa.load(path, sr=16000) ->
+// audio.load_contentvec_audio). At most three launches per call, whatever B is and whichever rows are asked for: the
+// channel-0 peak (only when some utterance holds float samples), the source rows, the mono rows (both of them).
 //
 // The arithmetic restates the per-file host path bit for bit (each row is np.array_equal to that path on the file alone):
 //   decode   audio.read_wav's f64 values: u8 (v - 128) / 128, s16 / 2^15, s24 / 2^23, s32 / 2^31, f32 / f64 as stored
@@ -12,6 +14,9 @@
 //            significand); a row whose rate already is sr_src holds these samples unfiltered
 //   mono     numpy's mean over the channels in f64 (sequential sum for 1-7 channels, ((c0+c1)+(c2+c3))+((c4+c5)+(c6+c7))
 //            for 8; then / channels), (float), the filter (also when up = down = 1), rint(v * 32768) clipped, / 32768
+//   float    the same (float) means; a row at another rate than sr_mono holds the filter's (float)acc, the value the
+//            mono row is about to round (audio.resample(quantize16=False)), a row already at sr_mono the means
+//            themselves, unfiltered (librosa.load does not resample at the native rate)
 //   filter   resample.hip's plan, index arithmetic and ascending-r sum, one fused multiply-add per tap in f64
 //            (resample_kernel's loop compiles to v_fmac_f64; fma() is written out here), (float) at the end
 // so nothing is folded or reordered and the file is built without fast-math.
@@ -19,7 +24,9 @@
 // Shape: block (b, chunk) owns kChunk consecutive output samples of row b. It walks them in tiles (the plan's `tile`,
 // the most outputs whose input span fits the LDS buffer), decodes a tile's input span once into LDS as f32 (s24 and
 // misaligned payloads make per-tap decoding the expensive part) and reads its taps phase-major, so one thread's taps
-// are contiguous. Outputs past the utterance's own length are written as zeros.
+// are contiguous. Outputs past the utterance's own length are written as zeros. The mono launch writes both mono rows
+// from the one decoded tile and the one pass over the taps: v to the float row, the rounded v to the quantised row; an
+// unfiltered float row copies the decoded mean out of the tile.
 #include "../../include/svc_hip.h"
 #include "common.h"
 #include "kernels.h"
@@ -40,6 +47,7 @@ constexpr int kPeakStride = 16;   // u64 words between two utterances' peak word
 struct PcmUtt {
   int64_t off, frames, n_src, n_mono;  // payload byte offset, frames, output samples of the two rows
   int32_t fmt, ch, plan_src, plan_mono;  // plan index into the call's plan table; -1: the row is the decoded samples
+  int32_t float_copy, pad_;              // the float mono row is the decoded means (the file already is at sr_mono)
 };
 struct PcmPlan {
   const double* hpm;
@@ -125,20 +133,22 @@ __device__ __forceinline__ float input_sample(const uint8_t* __restrict__ p, con
   return mag == 1.0f ? x : (float)((double)x / (double)mag);
 }
 
-// y[b][n], n < S: row b's sample n where n < its own length, zero after. See the head of the file.
+// y[b][n], n < S: row b's sample n where n < its own length, zero after. See the head of the file. yf (MONO only, or
+// null): the float mono rows, same shape; y may then be null (a plan of -1 then means an unfiltered float row).
 template <bool MONO>
 __global__ __launch_bounds__(kThreads) void load_pcm_kernel(const uint8_t* __restrict__ raw,
                                                             const PcmUtt* __restrict__ utt,
                                                             const PcmPlan* __restrict__ plans,
                                                             const unsigned long long* __restrict__ peak_bits,
                                                             int blocks_per_row, int64_t S, float* __restrict__ y,
-                                                            int32_t* __restrict__ info) {
+                                                            float* __restrict__ yf, int32_t* __restrict__ info) {
   __shared__ float xs[kSpan];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / blocks_per_row;
   const int chunk = blockIdx.x - b * blocks_per_row;
   const PcmUtt u = utt[b];
-  float* row = y + (int64_t)b * S;
+  float* row = y ? y + (int64_t)b * S : nullptr;
+  float* rowf = MONO && yf ? yf + (int64_t)b * S : nullptr;
   const int64_t n_lo = (int64_t)chunk * kChunk;
   const int64_t n_hi = n_lo + kChunk < S ? n_lo + kChunk : S;
   const int64_t n_out = MONO ? u.n_mono : u.n_src;
@@ -154,28 +164,30 @@ __global__ __launch_bounds__(kThreads) void load_pcm_kernel(const uint8_t* __res
     info[b] = cls | ((mf - mf == 0.0f) ? 0 : 4);
   }
   if (plan_idx < 0) {
-    for (int64_t n = n_lo + tid; n < n_hi; n += kThreads) row[n] = n < n_out ? input_sample<MONO>(p, u, n, mag) : 0.0f;
+    float* dst = MONO ? rowf : row;
+    for (int64_t n = n_lo + tid; n < n_hi; n += kThreads) dst[n] = n < n_out ? input_sample<MONO>(p, u, n, mag) : 0.0f;
     return;
   }
+  const bool copy_f = MONO && rowf && u.float_copy;
   const PcmPlan pl = plans[plan_idx];
   const int64_t n_in = u.frames;
   for (int64_t t0 = n_lo; t0 < n_hi; t0 += pl.tile) {
     const int64_t t1 = t0 + pl.tile < n_hi ? t0 + pl.tile : n_hi;
-    int64_t lo = 0;
+    int64_t lo = 0, span = 0;
     if (t0 < n_out) {  // (block-uniform) decode the inputs of outputs [t0, min(t1, n_out)) once
       const int64_t c1 = t1 < n_out ? t1 : n_out;
       lo = (t0 + pl.pre_remove) * pl.down / pl.up - (pl.per_phase - 1);
       if (lo < 0) lo = 0;
       int64_t hi = (c1 - 1 + pl.pre_remove) * pl.down / pl.up;
       if (hi > n_in - 1) hi = n_in - 1;
-      const int64_t span = hi - lo + 1;
+      span = hi - lo + 1;
       if (span > kSpan) return;  // never: the host sized `tile` for kSpan (the row keeps the caller's fill)
       __syncthreads();           // the previous tile's reads
       for (int64_t i = tid; i < span; i += kThreads) xs[i] = input_sample<MONO>(p, u, lo + i, mag);
       __syncthreads();
     }
     for (int64_t n = t0 + tid; n < t1; n += kThreads) {
-      float v = 0.0f;
+      float v = 0.0f, vf = 0.0f;
       if (n < n_out) {
         const int64_t j = (n + pl.pre_remove) * pl.down;  // resample_kernel's indices
         const int k0 = (int)(j % pl.up);
@@ -189,13 +201,17 @@ __global__ __launch_bounds__(kThreads) void load_pcm_kernel(const uint8_t* __res
         double acc = 0.0;
         for (int64_t r = r_lo; r <= r_hi; ++r) acc = fma(h[r], (double)x0[-r], acc);
         v = (float)acc;
-        if (MONO) {  // resample_kernel's quantize16
+        if (MONO) {
+          // the float row: v, or sample n itself where the file is at sr_mono (in the tile: up = down = 1)
+          vf = !copy_f ? v : (n >= lo && n - lo < span) ? xs[n - lo] : input_sample<MONO>(p, u, n, mag);
+          // resample_kernel's quantize16
           double q = rint((double)v * 32768.0);
           q = q < -32768.0 ? -32768.0 : (q > 32767.0 ? 32767.0 : q);
           v = (float)(q / 32768.0);
         }
       }
-      row[n] = v;
+      if (row) row[n] = v;
+      if (MONO && rowf) rowf[n] = vf;
     }
   }
 }
@@ -223,19 +239,22 @@ RatePlan rate_plan(int sr_in, int sr_out) {
 
 }  // namespace
 
-// The host half of svc_load_pcm (stage_features.hip owns the context and its ring): argument checks before any HIP call, one
+// The host half of svc_load_pcm and svc_load_pcm_ex (`ex`: which of the two words the messages; stage_features.hip owns the context and its ring): argument checks before any HIP call, one
 // staged table [PcmUtt x B | PcmPlan x n_plans | zeroed peak words], then the launches. `ring` and `device` point into
 // the context and are read only after the checks.
 int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
              const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
-             float* y_src, int sr_mono, int64_t S_mono, float* y_mono, int32_t* info, hipStream_t s) {
+             float* y_src, int sr_mono, int64_t S_mono, float* y_mono, float* y_mono_float, bool ex, int32_t* info,
+             hipStream_t s) {
   SVC_REQUIRE(raw, "load_pcm: null raw");
   SVC_REQUIRE(byte_off && n_frames && format && channels && sr_in, "load_pcm: null %s table",
               !byte_off ? "byte_off" : !n_frames ? "n_frames" : !format ? "format" : !channels ? "channels" : "sr_in");
-  SVC_REQUIRE(y_src || y_mono, "load_pcm: null y_src and y_mono (nothing to compute)");
+  SVC_REQUIRE(y_src || y_mono || y_mono_float, "load_pcm: null y_src and y_mono%s (nothing to compute)",
+              ex ? " and y_mono_float" : "");
+  const bool want_mono = y_mono || y_mono_float;
   SVC_REQUIRE(B >= 1, "load_pcm: B=%d", B);
   SVC_REQUIRE(!y_src || (sr_src >= 1 && S_src >= 1), "load_pcm: sr_src=%d S_src=%lld", sr_src, (long long)S_src);
-  SVC_REQUIRE(!y_mono || (sr_mono >= 1 && S_mono >= 1), "load_pcm: sr_mono=%d S_mono=%lld", sr_mono, (long long)S_mono);
+  SVC_REQUIRE(!want_mono || (sr_mono >= 1 && S_mono >= 1), "load_pcm: sr_mono=%d S_mono=%lld", sr_mono, (long long)S_mono);
   std::vector<PcmUtt> utt(B);
   std::vector<std::pair<int, int>> rates;  // the call's distinct (sr_in, sr_out)
   std::vector<RatePlan> rplans;
@@ -262,6 +281,7 @@ int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const i
     u.ch = channels[b];
     u.n_src = u.n_mono = 0;
     u.plan_src = u.plan_mono = -1;
+    u.float_copy = u.pad_ = 0;
     any_float |= u.fmt == SVC_PCM_F32 || u.fmt == SVC_PCM_F64;
     max_frames = std::max(max_frames, u.frames);
     if (y_src) {
@@ -270,17 +290,19 @@ int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const i
                   (long long)S_src);
       if (sr_in[b] != sr_src) u.plan_src = plan_index(sr_in[b], sr_src);
     }
-    if (y_mono) {
+    if (want_mono) {
       u.n_mono = svc_resample_len(u.frames, sr_in[b], sr_mono);
       SVC_REQUIRE(u.n_mono <= S_mono, "load_pcm: utterance %d: %lld mono samples, S_mono %lld", b, (long long)u.n_mono,
                   (long long)S_mono);
-      u.plan_mono = plan_index(sr_in[b], sr_mono);
+      u.float_copy = y_mono_float && sr_in[b] == sr_mono;
+      // the quantised row always goes through the filter; a float row alone needs no plan where it is a copy
+      if (y_mono || !u.float_copy) u.plan_mono = plan_index(sr_in[b], sr_mono);
     }
   }
   for (size_t i = 0; i < rplans.size(); ++i)
     SVC_REQUIRE(rplans[i].taps > 0 && rplans[i].tile >= 1, "load_pcm: rate ratio %d -> %d is too large for the filter tile",
                 rates[i].first, rates[i].second);
-  const int64_t bpr_src = y_src ? cdiv64(S_src, kChunk) : 0, bpr_mono = y_mono ? cdiv64(S_mono, kChunk) : 0;
+  const int64_t bpr_src = y_src ? cdiv64(S_src, kChunk) : 0, bpr_mono = want_mono ? cdiv64(S_mono, kChunk) : 0;
   const int64_t bpr_peak = cdiv64(max_frames, kPeakChunk);
   SVC_REQUIRE(bpr_src * B < (1ll << 31) && bpr_mono * B < (1ll << 31) && bpr_peak * B < (1ll << 31),
               "load_pcm: batch of %d rows too large", B);
@@ -319,15 +341,15 @@ int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const i
   if (y_src && bpr_src > 0) {
     const int tok = prof_begin("load_pcm_src", 0.0, 0.0, s);
     hipLaunchKernelGGL(load_pcm_kernel<false>, dim3((unsigned)(bpr_src * B)), dim3(kThreads), 0, s, r8, d_utt, d_plans,
-                       d_peak, (int)bpr_src, S_src, y_src, info_left);
+                       d_peak, (int)bpr_src, S_src, y_src, (float*)nullptr, info_left);
     prof_end(tok, s);
     SVC_LAUNCH_CHECK();
     info_left = nullptr;
   }
-  if (y_mono && bpr_mono > 0) {
+  if (want_mono && bpr_mono > 0) {
     const int tok = prof_begin("load_pcm_mono", 0.0, 0.0, s);
     hipLaunchKernelGGL(load_pcm_kernel<true>, dim3((unsigned)(bpr_mono * B)), dim3(kThreads), 0, s, r8, d_utt, d_plans,
-                       d_peak, (int)bpr_mono, S_mono, y_mono, info_left);
+                       d_peak, (int)bpr_mono, S_mono, y_mono, y_mono_float, info_left);
     prof_end(tok, s);
     SVC_LAUNCH_CHECK();
   }

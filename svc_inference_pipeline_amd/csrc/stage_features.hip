@@ -191,7 +191,16 @@ svc_status svc_load_pcm(svc_ctx* c, const void* raw, int B, const int64_t* byte_
   SVC_REQUIRE(c, "load_pcm: null context");
   // the context is read only once the arguments have passed (load_pcm.hip checks them before any HIP call)
   return load_pcm(&c->lens_load, &c->device, raw, B, byte_off, n_frames, format, channels, sr_in, sr_src, S_src, y_src,
-                  sr_mono, S_mono, y_mono, info, (hipStream_t)stream);
+                  sr_mono, S_mono, y_mono, nullptr, false, info, (hipStream_t)stream);
+}
+
+svc_status svc_load_pcm_ex(svc_ctx* c, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
+                           const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,
+                           int64_t S_src, float* y_src, int sr_mono, int64_t S_mono, float* y_mono,
+                           float* y_mono_float, int32_t* info, void* stream) {
+  SVC_REQUIRE(c, "load_pcm: null context");
+  return load_pcm(&c->lens_load, &c->device, raw, B, byte_off, n_frames, format, channels, sr_in, sr_src, S_src, y_src,
+                  sr_mono, S_mono, y_mono, y_mono_float, true, info, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,7 @@ converted wav, on one MI355X through libsvc_hip.so.
     python -m svc_inference_pipeline_amd.infer --wav a.wav b.wav c.wav ...   # several files: one ragged batch
 
 Same sequence as the reference: acoustic features (mel, energy, Praat F0) -> pitch shift to the target
-singer -> Whisper content features -> DiffSVC sampler (DDPM-1000 by default, PLMS with --fast, as
+singer -> Whisper (and / or ContentVec, --hubert-ckpt) content features -> DiffSVC sampler (DDPM-1000 by default, PLMS with --fast, as
 svc_model_inference's fast_inference) -> de-normalisation -> BigVGAN -> fade -> 16-bit wav (peak 0.9, 50 ms of
 silence each side). Checkpoint paths default to the config's svc_model_path / vocoder_model_path. Without
 checkpoints the run needs --random-weights (seeded weights of the reference architectures: plumbing and
@@ -23,24 +23,46 @@ import torch
 from . import audio as A
 from . import config as C
 from . import weights as W
-from .pipeline import SVCPipeline
+from .pipeline import SVCPipeline, hubert_content_type, wants_float16k
 from .runtime import SVCEngine
 
 
-def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckpt=None, random_weights=None, seed=0):
+def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckpt=None, random_weights=None, seed=0,
+                 hubert_ckpt=None):
     """Engine from the reference's checkpoints, or from seeded random weights when random_weights names a
-    Whisper size ("medium" or "tiny-test"); checkpoints and random weights do not mix."""
+    Whisper size ("medium" or "tiny-test"); checkpoints and random weights do not mix.
+    When the config names a HuBERT / ContentVec content type the engine needs that model too: hubert_ckpt (fairseq's
+    layout, weights.load_checkpoints), or with random_weights a seeded state of HUBERT_DIMS["tiny-test"] for
+    "tiny-test" and of HUBERT_DIMS["contentvec"] otherwise (the type's input_content_dim is set to its width)."""
+    types = list(cfg.mapper.content_feature)
+    cv = hubert_content_type(cfg)
     if random_weights:
-        dims = W.WHISPER_DIMS[random_weights]
-        if dims["n_audio_state"] != cfg.mapper.input_content_dim["whisper"]:
-            cfg.mapper.input_content_dim["whisper"] = dims["n_audio_state"]
-        return SVCEngine(cfg, device, whisper_state=W.make_whisper_state(dims, seed),
-                         mapper_state=W.make_mapper_state(cfg.mapper, seed),
-                         vocoder_state=W.make_vocoder_state(cfg.vocoder, seed))
-    if not (mapper_ckpt and vocoder_ckpt and whisper_ckpt):
+        kw = {}
+        if "whisper" in types:
+            dims = W.WHISPER_DIMS[random_weights]
+            if dims["n_audio_state"] != cfg.mapper.input_content_dim["whisper"]:
+                cfg.mapper.input_content_dim["whisper"] = dims["n_audio_state"]
+            kw["whisper_state"] = W.make_whisper_state(dims, seed)
+        if cv:
+            hd = W.HUBERT_DIMS["tiny-test" if random_weights == "tiny-test" else "contentvec"]
+            cfg.mapper.input_content_dim[cv] = hd["final_dim"]
+            kw.update(hubert_state=W.make_hubert_state(hd, seed), hubert_output_layer=hd["output_layer"])
+        return SVCEngine(cfg, device, mapper_state=W.make_mapper_state(cfg.mapper, seed),
+                         vocoder_state=W.make_vocoder_state(cfg.vocoder, seed), **kw)
+    if cv and not hubert_ckpt:
+        raise SystemExit(f"the config names the content feature {cv!r}: need --hubert-ckpt (the ContentVec / HuBERT "
+                         "checkpoint; default: the config's contentVec_model), or --random-weights")
+    need_whisper = "whisper" in types
+    if not (mapper_ckpt and vocoder_ckpt and (whisper_ckpt or not need_whisper)):
         raise SystemExit("need --mapper-ckpt, --vocoder-ckpt and --whisper-ckpt (or --random-weights)")
-    st = W.load_checkpoints(mapper_ckpt, vocoder_ckpt, whisper_ckpt)
-    return SVCEngine(cfg, device, whisper_state=st["whisper"], mapper_state=st["mapper"], vocoder_state=st["vocoder"])
+    st = W.load_checkpoints(mapper_ckpt, vocoder_ckpt, whisper_ckpt if need_whisper else None,
+                            hubert_path=hubert_ckpt if cv else None)
+    kw = {}
+    if cv:  # utils/hubert.py:42 output_layer=9, or every layer of a shallower model
+        kw.update(hubert_state=st["hubert"],
+                  hubert_output_layer=W.hubert_dims_from_state(st["hubert"])["output_layer"])
+    return SVCEngine(cfg, device, whisper_state=st.get("whisper"), mapper_state=st["mapper"],
+                     vocoder_state=st["vocoder"], **kw)
 
 
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
@@ -48,7 +70,11 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
     the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16)."""
     # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
-    (wav24,), (wav16,) = A.load_batch([wav_path], cfg.fs, engine)
+    wav16f = None
+    if wants_float16k(cfg):  # and utils/hubert.py:137-143's float 16 kHz copy from the same stage
+        (wav24,), (wav16,), (wav16f,) = A.load_batch([wav_path], cfg.fs, engine, float16k=True)
+    else:
+        (wav24,), (wav16,) = A.load_batch([wav_path], cfg.fs, engine)
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
@@ -56,6 +82,7 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
     utt = torch.zeros(1, dtype=torch.int32, device=device)
     res = SVCPipeline(engine, f0_method=f0_method).convert(wav24[None].contiguous(), wav16[None].contiguous(), singer,
                                       fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=utt,
+                                      wav16_float=None if wav16f is None else wav16f[None].contiguous(),
                                       pcm16=pcm16)
     return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
@@ -68,10 +95,14 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
-    w24, w16 = A.load_batch(list(wav_paths), cfg.fs, engine)  # all files decoded and resampled in one device stage
+    w16f = None  # all files decoded and resampled in one device stage
+    if wants_float16k(cfg):
+        w24, w16, w16f = A.load_batch(list(wav_paths), cfg.fs, engine, float16k=True)
+    else:
+        w24, w16 = A.load_batch(list(wav_paths), cfg.fs, engine)
     sid = int(singers[singer_name])
-    wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), fast_inference=fast_inference,
-                                            speedup=speedup, seed=seed, pcm16=pcm16)
+    wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), wavs16_float=w16f,
+                                            fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16)
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
     return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
@@ -90,6 +121,9 @@ def main(argv=None):
     ap.add_argument("--mapper-ckpt", default=None)
     ap.add_argument("--vocoder-ckpt", default=None)
     ap.add_argument("--whisper-ckpt", default=None)
+    ap.add_argument("--hubert-ckpt", default=None,
+                    help="ContentVec / HuBERT checkpoint in fairseq's layout, for a config whose content features name "
+                         "contentvec (default: the config's contentVec_model)")
     ap.add_argument("--random-weights", default=None, choices=sorted(W.WHISPER_DIMS))
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--f0-method", default="parselmouth", choices=("parselmouth", "pyin"),
@@ -101,7 +135,9 @@ def main(argv=None):
     mapper = args.mapper_ckpt or getattr(cfg, "svc_model_path", None)
     vocoder = args.vocoder_ckpt or getattr(cfg, "vocoder_model_path", None)
     print("Loading mapper and vocoder...", flush=True)
-    engine = build_engine(cfg, args.device, mapper, vocoder, args.whisper_ckpt, args.random_weights, args.seed)
+    hubert = args.hubert_ckpt or getattr(cfg, "contentVec_model", None)
+    engine = build_engine(cfg, args.device, mapper, vocoder, args.whisper_ckpt, args.random_weights, args.seed,
+                          hubert_ckpt=hubert)
     if args.out and len(args.wav) > 1:
         raise SystemExit("--out names one output file: omit it when converting several files")
     t0 = time.time()

@@ -34,6 +34,18 @@ MAX_MAPPED = 2812             # utils/whisper.py:56 (1500 * 15 // 8)
 HUBERT_CONTENT_TYPES = ("contentvec", "content_vector", "hubert")  # config/config.json:35 names it content_vector
 
 
+def hubert_content_type(cfg):
+    """The HuBERT / ContentVec content type cfg.mapper.content_feature names, or None."""
+    types = getattr(getattr(cfg, "mapper", None), "content_feature", None) or ()
+    return next((t for t in types if t in HUBERT_CONTENT_TYPES), None)
+
+
+def wants_float16k(cfg):
+    """The file entry points load the float 16 kHz rows (audio.load_batch(float16k=True)) exactly when the
+    configuration names a HuBERT / ContentVec content type."""
+    return hubert_content_type(cfg) is not None
+
+
 @dataclass
 class ConvertResult:
     wav: torch.Tensor        # f32 [B, T*hop] converted audio (before save_audio's peak normalisation)
@@ -289,13 +301,22 @@ class SVCPipeline:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
                                         pcm16)
 
-    def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False):
+    def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
+                      float16k=None):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
-        batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it."""
+        batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
+        float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
+        HuBERT / ContentVec reads them as `wavs16_float`, what utils/hubert.py:137-143 feeds it; None (default): when
+        the configuration names a HuBERT content type (wants_float16k); False: HuBERT is fed Whisper's int16-grid rows.
+        Without a HuBERT type and with None or False, load_batch is called without the keyword."""
         from . import audio as A
-        wavs24, wavs16 = A.load_batch(sources, self.engine.cfg.fs, self.engine)
-        return self.convert_ragged(wavs24, wavs16, singers, fast_inference=fast_inference, speedup=speedup, seed=seed,
-                                   utt_ids=utt_ids, pcm16=pcm16)
+        if wants_float16k(self.engine.cfg) if float16k is None else float16k:
+            wavs24, wavs16, wavs16_float = A.load_batch(sources, self.engine.cfg.fs, self.engine, float16k=True)
+        else:
+            wavs24, wavs16 = A.load_batch(sources, self.engine.cfg.fs, self.engine)
+            wavs16_float = None
+        return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float, fast_inference=fast_inference,
+                                   speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16)
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
                         pcm16=False):

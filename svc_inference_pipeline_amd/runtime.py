@@ -382,12 +382,14 @@ class SVCEngine:
                   _ptr(wav), _ptr(mel), _stream())
         return (wav, mel) if return_mel else wav
 
-    def load_pcm(self, infos, fs=None, sr_mono=16000):
+    def load_pcm(self, infos, fs=None, sr_mono=16000, float_mono=False):
         """The input end for a batch of parsed wavs (audio.WavInfo: format code, channels, rate, frames, payload view):
-        one host concatenation of the payloads, one upload, one svc_load_pcm call -> (y_src f32 [B, S_src] at `fs`
+        one host concatenation of the payloads, one upload, one svc_load_pcm_ex call -> (y_src f32 [B, S_src] at `fs`
         (default: the config's), y_mono f32 [B, S_mono] at sr_mono on the int16 grid, n_src, n_mono (host ints [B]: each
         row's own samples, zeros after them), info int32 [B] on the device (bits 0-1 the normalisation class, bit 2
-        non-finite source samples)). Row b is bit for bit audio.load_audio / audio.load_whisper_audio of that file."""
+        non-finite source samples)). Row b is bit for bit audio.load_audio / audio.load_whisper_audio of that file.
+        float_mono=True: a sixth value, y_mono_float f32 [B, S_mono], HuBERT / ContentVec's float copy at sr_mono from
+        the same launch as y_mono (row b is audio.load_contentvec_audio of that file; n_mono is its length too)."""
         fs = int(self.cfg.fs if fs is None else fs)
         B = len(infos)
         if B < 1:
@@ -405,12 +407,16 @@ class SVCEngine:
             n_mono = [int(lib.svc_resample_len(i.n_frames, i.sr, sr_mono)) for i in infos]
             y_src = torch.empty(B, max(1, max(n_src)), device=dev, dtype=torch.float32)
             y_mono = torch.empty(B, max(1, max(n_mono)), device=dev, dtype=torch.float32)
+            y_float = torch.empty_like(y_mono) if float_mono else None
             info = torch.empty(B, device=dev, dtype=torch.int32)
             i64, i32 = ctypes.c_int64 * B, ctypes.c_int32 * B
-            _lib.call("svc_load_pcm", self._ctx, _ptr(raw), B, i64(*offs.tolist()), i64(*[i.n_frames for i in infos]),
-                      i32(*[i.format for i in infos]), i32(*[i.channels for i in infos]), i32(*[i.sr for i in infos]),
-                      fs, y_src.shape[1], _ptr(y_src), int(sr_mono), y_mono.shape[1], _ptr(y_mono), _ptr(info),
+            _lib.call("svc_load_pcm_ex", self._ctx, _ptr(raw), B, i64(*offs.tolist()),
+                      i64(*[i.n_frames for i in infos]), i32(*[i.format for i in infos]),
+                      i32(*[i.channels for i in infos]), i32(*[i.sr for i in infos]), fs, y_src.shape[1], _ptr(y_src),
+                      int(sr_mono), y_mono.shape[1], _ptr(y_mono), _ptr(y_float), _ptr(info),
                       ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if float_mono:
+            return y_src, y_mono, n_src, n_mono, info, y_float
         return y_src, y_mono, n_src, n_mono, info
 
     def pcm16(self, wav, n_samples=None, add_silence=True, turn_up=True, volume_peak=0.9, return_peak=False):

@@ -19,7 +19,8 @@ Streams: submit() records an event on the caller's current stream, and the worke
 reads the request's tensors, so inputs produced by kernels still in flight on the caller's stream are safe to
 submit. A result is a view into the batch's output, recorded for use on the submitting stream (record_stream), and
 the future resolves once it is complete. File requests carry no tensors: the worker decodes all of a batch's files in
-one audio.load_batch (svc_load_pcm) on its own stream. The engine's lock (SVCEngine.lock) serialises the worker's conversions with
+one audio.load_batch (svc_load_pcm; with a HuBERT / ContentVec configuration svc_load_pcm_ex, which also gives each its
+float 16 kHz input `wav16_float`) on its own stream. The engine's lock (SVCEngine.lock) serialises the worker's conversions with
 any direct use of the same engine.
 """
 import collections
@@ -34,7 +35,7 @@ import torch
 
 from . import _lib
 from . import audio as A
-from .pipeline import SVCPipeline
+from .pipeline import SVCPipeline, wants_float16k
 from .runtime import mel_frames
 
 
@@ -51,6 +52,7 @@ class _Request:
     stream: object = None   # the submitting stream
     future: Future = field(default_factory=Future)
     file: object = None     # audio.WavInfo of a submit_file request (wav24 / wav16 are decoded by the worker)
+    float16k: bool = False  # a file request whose decoding also fills wav16_float (a HuBERT configuration)
 
 
 class SVCServer:
@@ -70,6 +72,7 @@ class SVCServer:
         cfg = pipeline.engine.cfg
         self._frames = lambda n: mel_frames(n, cfg.n_fft, cfg.hop_length)
         self._fs = getattr(cfg, "fs", None)  # the model rate file requests are resampled to
+        self._float16k = wants_float16k(cfg)  # file requests are decoded with the float 16 kHz rows HuBERT reads
         self._ids = itertools.count()
         self._pending = []
         self._cv = threading.Condition()
@@ -104,7 +107,10 @@ class SVCServer:
         """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
         the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
         the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
-        requests). A bad file (unreadable header, <= 2 frames, non-finite samples) fails its own future only."""
+        requests). A bad file (unreadable header, <= 2 frames, non-finite samples) fails its own future only.
+        When the configuration names a HuBERT / ContentVec content type the decode also gives the request its float
+        16 kHz row (audio.load_contentvec_audio of the file), so for batching it counts as a request with `wav16_float`:
+        it shares a batch with tensor requests that carry one, never with tensor requests that do not."""
         req = self._file_request(src, singer, utt_id)
         if req.future.done():
             return req.future
@@ -130,6 +136,7 @@ class SVCServer:
             req.future.set_exception(exc)
             return req
         req.file = info
+        req.float16k = self._float16k
         req.frames = self._frames(int(_lib.load().svc_resample_len(info.n_frames, info.sr, int(self._fs))))
         return req
 
@@ -157,11 +164,16 @@ class SVCServer:
         for r in self._pending[1:]:
             if len(batch) == self.max_batch:
                 break
-            if lo <= r.frames <= hi and (r.wav16_float is None) == (head.wav16_float is None):
+            if lo <= r.frames <= hi and self._has_float(r) == self._has_float(head):
                 batch.append(r)
         taken = set(map(id, batch))
         self._pending = [r for r in self._pending if id(r) not in taken]
         return batch
+
+    @staticmethod
+    def _has_float(r):
+        """The request holds a float 16 kHz input, or will once the worker has decoded its file."""
+        return r.wav16_float is not None or r.float16k
 
     def _ready(self):
         """A batch may run: it is full, the oldest request has waited max_wait_s, or the server is closing."""
@@ -192,15 +204,21 @@ class SVCServer:
         files = [r for r in batch if r.file is not None]
         if not files:
             return batch
+        w16f = [None] * len(files)
         try:
-            w24, w16, errors = A.load_batch([r.file for r in files], self._fs, self.pipeline.engine, on_error="return")
+            if self._float16k:
+                w24, w16, w16f, errors = A.load_batch([r.file for r in files], self._fs, self.pipeline.engine,
+                                                      on_error="return", float16k=True)
+            else:
+                w24, w16, errors = A.load_batch([r.file for r in files], self._fs, self.pipeline.engine,
+                                                on_error="return")
         except Exception as exc:  # noqa: BLE001 - the decode itself failed: every file request of the batch
             w24, w16, errors = [None] * len(files), [None] * len(files), {i: exc for i in range(len(files))}
         for i, r in enumerate(files):
             if i in errors:
                 r.future.set_exception(errors[i])
             else:
-                r.wav24, r.wav16 = w24[i], w16[i]
+                r.wav24, r.wav16, r.wav16_float = w24[i], w16[i], w16f[i]
         return [r for r in batch if r.wav24 is not None]
 
     def _convert(self, batch):

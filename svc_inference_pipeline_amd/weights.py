@@ -323,6 +323,20 @@ def make_hubert_state(dims, seed=0):
     return sd
 
 
+def hubert_param_names(n_layer):
+    """The keys of make_hubert_state for a model of n_layer transformer layers, in its order."""
+    names = [f"feature_extractor.conv_layers.{i}.0.weight" for i in range(len(HUBERT_CONV_LAYERS))]
+    names += [f"feature_extractor.conv_layers.0.2.{n}" for n in ("weight", "bias")]
+    names += ["layer_norm.weight", "layer_norm.bias", "post_extract_proj.weight", "post_extract_proj.bias",
+              "encoder.pos_conv.0.weight_v", "encoder.pos_conv.0.weight_g", "encoder.pos_conv.0.bias",
+              "encoder.layer_norm.weight", "encoder.layer_norm.bias"]
+    for i in range(n_layer):
+        for m in ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.out_proj",
+                  "self_attn_layer_norm", "final_layer_norm", "fc1", "fc2"):
+            names += [f"encoder.layers.{i}.{m}.weight", f"encoder.layers.{i}.{m}.bias"]
+    return names + ["final_proj.weight", "final_proj.bias"]
+
+
 def hubert_dims_from_state(sd, output_layer=9):
     Cc = sd["feature_extractor.conv_layers.0.0.weight"].shape[0]
     D = sd["post_extract_proj.weight"].shape[0]
@@ -369,12 +383,26 @@ def _tensor_dict(sd, strip_module=True, prefix=None):
     return out
 
 
-def load_checkpoints(mapper_path=None, vocoder_path=None, whisper_path=None):
-    """The reference's three checkpoint formats -> {"mapper"|"vocoder"|"whisper": state dict of f32 arrays}.
+def _load_fairseq(path):
+    """torch.load(weights_only=True) of a fairseq checkpoint. Legacy fairseq files carry their options as an
+    argparse.Namespace under "args": that one class is allow-listed for the load, nothing else, and a file that
+    needs any other class fails here (never a full unpickle)."""
+    import argparse
+    with torch.serialization.safe_globals([argparse.Namespace]):
+        return torch.load(path, map_location="cpu", weights_only=True)
+
+
+def load_checkpoints(mapper_path=None, vocoder_path=None, whisper_path=None, hubert_path=None):
+    """The reference's checkpoint formats -> {"mapper"|"vocoder"|"whisper"|"hubert": state dict of f32 arrays}.
 
     mapper  utils/load_models.py:23-49   ckpt["state_dict"], keys of ModuleList([EncoderFramework, DiffSVC])
     vocoder utils/load_models.py:52-79   ckpt["generator_state_dict"], keys of Generator
     whisper utils/whisper_extractor/__init__.py:72-120  {"dims", "model_state_dict"}; the encoder half is kept
+    hubert  utils/hubert.py:14-28        fairseq's layout (checkpoint_utils.load_model_ensemble_and_task): ckpt["model"],
+                                         fairseq's key names as make_hubert_state produces them; every key that
+                                         make_hubert_state names for the file's own dimensions must be present
+                                         (ValueError naming the missing keys). No real ContentVec checkpoint was at
+                                         hand: this reader is pinned only to its own writer (save_checkpoints).
     "module." prefixes are stripped as the reference does. Loading is weights_only (no unpickling of code).
     Unlike the reference, which keeps random init for missing or mis-shaped keys, SVCEngine's native
     finalize rejects them (svc_ctx_finalize)."""
@@ -393,11 +421,24 @@ def load_checkpoints(mapper_path=None, vocoder_path=None, whisper_path=None):
         for k in ("n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer"):
             if k in dims and int(dims[k]) != int(got[k]):
                 raise ValueError(f"whisper checkpoint {whisper_path}: dims[{k}]={dims[k]} but weights give {got[k]}")
+    if hubert_path:
+        ckpt = _load_fairseq(hubert_path)
+        if not isinstance(ckpt, dict) or not isinstance(ckpt.get("model"), dict):
+            raise ValueError(f"hubert checkpoint {hubert_path}: no \"model\" state dict (fairseq's layout)")
+        sd = _tensor_dict(ckpt["model"])
+        layers = [int(k.split(".")[2]) for k in sd if k.startswith("encoder.layers.")]
+        missing = [k for k in hubert_param_names(1 + max(layers, default=0)) if k not in sd]
+        if missing:
+            raise ValueError(f"hubert checkpoint {hubert_path}: missing {missing[:5]}"
+                             f"{'...' if len(missing) > 5 else ''}")
+        out["hubert"] = sd
     return out
 
 
-def save_checkpoints(dirname, mapper_state=None, vocoder_state=None, whisper_state=None, module_prefix=False):
-    """Write states in the reference's checkpoint formats (tests and tools; the inverse of load_checkpoints)."""
+def save_checkpoints(dirname, mapper_state=None, vocoder_state=None, whisper_state=None, module_prefix=False,
+                     hubert_state=None):
+    """Write states in the reference's checkpoint formats (tests and tools; the inverse of load_checkpoints).
+    hubert_state goes out in fairseq's layout, {"model": state dict} (never prefixed)."""
     import os
     os.makedirs(dirname, exist_ok=True)
     pre = "module." if module_prefix else ""
@@ -415,5 +456,8 @@ def save_checkpoints(dirname, mapper_state=None, vocoder_state=None, whisper_sta
         torch.save({"dims": whisper_dims_from_state(whisper_state),
                     "model_state_dict": {k: torch.from_numpy(np.asarray(v)) for k, v in whisper_state.items()}},
                    paths["whisper"])
+    if hubert_state is not None:
+        paths["hubert"] = os.path.join(dirname, "hubert.pt")
+        torch.save({"model": {k: torch.from_numpy(np.asarray(v)) for k, v in hubert_state.items()}}, paths["hubert"])
     return paths
 

@@ -2,7 +2,8 @@
 built in memory as whole wav files.
 
   (a) HIP-event time of one svc_load_pcm call (payloads already on the device): warm median of `reps` (>= 20) calls on
-      one input, and again rotating over distinct inputs; the launches alone from the library's own events;
+      one input, and again rotating over distinct inputs; the launches alone from the library's own events, and once
+      more through svc_load_pcm_ex with the float 16 kHz rows (the mono launch then stores two rows);
   (b) end to end on this box, host clock around work that ends synchronised: audio.load_batch on the 32 byte strings
       (header parse, one concatenation, one upload, one call) against what a caller did before, 32 x
       (audio.load_audio + audio.load_whisper_audio) on the same files on disk; median of 5 each, the two alternating;
@@ -132,6 +133,25 @@ def main():
         _lib.profile_filter("")
         kern = {k: v["ms"] / v["launches"] for k, v in stats.items()}
         launches_per_call = sum(v["launches"] for v in stats.values()) / 48
+        y_float = torch.empty_like(y_mono)
+
+        def call_ex(k):
+            _lib.call("svc_load_pcm_ex", eng._ctx, ctypes.c_void_p(raws[k].data_ptr()), B, *tables, fs,
+                      y_src.shape[1], ctypes.c_void_p(y_src.data_ptr()), A.WHISPER_SR, y_mono.shape[1],
+                      ctypes.c_void_p(y_mono.data_ptr()), ctypes.c_void_p(y_float.data_ptr()),
+                      ctypes.c_void_p(info.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+        for i in range(n_rot):
+            call_ex(i)
+        torch.cuda.synchronize()
+        _lib.profile_filter("load_pcm")
+        _lib.profile_enable(True)
+        for i in range(48):
+            call_ex(i % n_rot)
+        stats = _lib.profile_read()
+        _lib.profile_enable(False)
+        _lib.profile_filter("")
+        kern_float = {k: round(v["ms"] / v["launches"], 5) for k, v in sorted(stats.items())}
         del raws
 
         # (b) end to end, against the per-file path; (c) equal results
@@ -163,7 +183,7 @@ def main():
             "svc_load_pcm_ms_warm_median": round(warm_med, 5), "svc_load_pcm_ms_warm_min": round(warm_min, 5),
             "svc_load_pcm_ms_rotating_median": round(rot_med, 5), "svc_load_pcm_ms_rotating_min": round(rot_min, 5),
             "kernel_ms_rotating_mean": {k: round(v, 5) for k, v in sorted(kern.items())},
-            "launches_per_call": launches_per_call,
+            "kernel_ms_rotating_mean_with_float_row": kern_float, "launches_per_call": launches_per_call,
             "e2e_load_batch_ms": round(batched_ms, 3), "e2e_load_batch_from_paths_ms": round(batched_paths_ms, 3),
             "e2e_per_file_load_audio_plus_load_whisper_audio_ms": round(per_file_ms, 3),
             "e2e_ratio_per_file_over_batched": round(per_file_ms / batched_ms, 3),
