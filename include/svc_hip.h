@@ -92,7 +92,9 @@ svc_status svc_ctx_get_config(svc_ctx* ctx, const char* key, double* value);
 int svc_config_key_known(const char* key);
 svc_status svc_ctx_add_param(svc_ctx* ctx, const char* name, const float* host, int ndim, const int64_t* shape);
 svc_status svc_ctx_finalize(svc_ctx* ctx);
-/* bytes of device memory held by packed weights / by the workspace arena */
+/* bytes of device memory held by packed weights / by the workspace arena. The arena only grows, and each stage call
+   sizes it by counting its own buffers: workspace_bytes is exactly what the largest stage call so far needed, with no
+   slack (the feature stages' own workspace, svc_f0_ac / svc_f0_pyin, is not included). */
 svc_status svc_ctx_memory(svc_ctx* ctx, int64_t* weight_bytes, int64_t* workspace_bytes);
 /* the context's sub-stream `index` (< 8; created on first use, owned by the context): lets a caller overlap
    svc_f0_ac with the content encoder without creating a stream of its own */

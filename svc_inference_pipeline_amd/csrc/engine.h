@@ -1,5 +1,6 @@
-// The engine's own types and the helpers its files share: the context (svc_ctx), packed weights, the workspace arena
-// and the sub-batch fork / join. Included by engine.hip, finalize.hip, the stage_*.hip files and ops.hip only.
+// The engine's own types and the helpers its files share: the context (svc_ctx), packed weights and the sub-batch
+// fork / join (the workspace arena is arena.h). Included by engine.hip, finalize.hip, the stage_*.hip files and ops.hip
+// only.
 #pragma once
 #include <map>
 #include <string>
@@ -9,31 +10,6 @@
 #include "kernels.h"
 
 namespace svc {
-
-// ---------------------------------------------------------------------------- arena
-struct Arena {
-  char* base = nullptr;
-  size_t cap = 0, off = 0, peak = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return SVC_OK;
-    if (base) SVC_HIP_CHECK(hipFree(base));
-    base = nullptr;
-    cap = 0;
-    SVC_HIP_CHECK(hipMalloc(&base, bytes));
-    cap = bytes;
-    return SVC_OK;
-  }
-  void reset() { off = 0; }
-  template <typename T>
-  T* get(size_t n) {
-    size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-    if (off + bytes > cap) return nullptr;
-    T* p = reinterpret_cast<T*>(base + off);
-    off += bytes;
-    if (off > peak) peak = off;
-    return p;
-  }
-};
 
 constexpr int kMaxSubStreams = 8;
 
@@ -311,10 +287,3 @@ struct SubBatches {
     }                                                                       \
     SVC_HIP_CHECK(hipSetDevice((c)->device));                               \
   } while (0)
-
-#define WS_GET(T, var, n)                                                               \
-  T* var = c->ws.get<T>((size_t)(n));                                                   \
-  if (!var) {                                                                           \
-    set_error("workspace exhausted at %s (need %zu bytes more)", #var, (size_t)(n) * sizeof(T)); \
-    return SVC_ERR_STATE;                                                               \
-  }

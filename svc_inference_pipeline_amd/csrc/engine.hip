@@ -127,6 +127,17 @@ int ensure_dyn_lds(const void* fn, int bytes) {
   return SVC_OK;
 }
 
+// the arena's device memory (arena.h). hipFree waits for the device, so no launch still reads the block it replaces.
+int Arena::reserve(size_t bytes) {
+  if (bytes <= cap) return SVC_OK;
+  if (base) SVC_HIP_CHECK(hipFree(base));
+  base = nullptr;
+  cap = 0;
+  SVC_HIP_CHECK(hipMalloc(&base, bytes));
+  cap = bytes;
+  return SVC_OK;
+}
+
 double cfgv(svc_ctx* c, const char* k, double d) {
   auto it = c->cfg.find(k);
   return it == c->cfg.end() ? d : it->second;

@@ -727,14 +727,6 @@ __global__ void f0_path_kernel(F0Params P, F0Out o, int* __restrict__ psi, int T
 // (and never past bmax: the sums stop at the end of r)
 static int f0_rw(const F0Params& P) { return std::min((std::min(P.maxlag, P.bmax) + 72 + 1) & ~1, P.bmax + 1); }
 
-size_t f0_workspace_bytes(int B, int64_t n, double fs, double ts, double floor_hz) {
-  F0Params P = f0_params(n, fs, ts, floor_hz, 800.0);
-  if (P.nf < 1) return 4096;
-  const size_t nf = (size_t)B * P.nf;
-  return nf * F0_MAXC * (8 + 8 + 4 + 4 + 4) + nf * (4 + 8) + nf * (size_t)f0_rw(P) * 8 + (size_t)B * F0_GP * 3 * 8 +
-         9 * 4096;
-}
-
 // The context's per-parameter-set tables: [Hann window: nw][its normalised autocorrelation wR: bmax + 1][pad to even]
 // [quarter twiddles W_nfft^m = (cos, -sin)(2 pi m / nfft), m < nfft / 4, as (re, im) pairs]
 size_t f0_table_doubles(double fs, double floor_hz) {
@@ -779,8 +771,8 @@ static int launch_f0_frames(const float* wav, int B, int64_t n, const F0Params& 
 // is computed on its own samples exactly as a clip of that length, and written zero past T_b[b]. The per-utterance
 // frame grids are staged to the device through `ring`. tab: the device copy of f0_tables(fs, floor_hz).
 int f0_praat_ac(const float* wav, int B, int64_t n, double fs, double ts, double floor_hz, double ceiling_hz,
-                double voicing, int T, double* f0_out, void* workspace, size_t ws_bytes, const double* tab,
-                hipStream_t s, const int64_t* n_b, const int* T_b, StageRing* ring) {
+                double voicing, int T, double* f0_out, Arena& ws, const double* tab, hipStream_t s,
+                const int64_t* n_b, const int* T_b, StageRing* ring) {
   F0Params P = f0_params(n, fs, ts, floor_hz, ceiling_hz);
   SVC_REQUIRE(P.nf >= 1, "f0: sound (%lld samples) shorter than the 3-period window", (long long)n);
   const int hop = (int)llround(ts * fs);
@@ -813,25 +805,23 @@ int f0_praat_ac(const float* wav, int B, int64_t n, double fs, double ts, double
   P.octave_cost = 0.01;
   P.octave_jump = 0.35;
   P.vuv_cost = 0.14;
-  SVC_REQUIRE(ws_bytes >= f0_workspace_bytes(B, n, fs, ts, floor_hz), "f0: workspace too small");
-  char* w = (char*)workspace;
-  auto take = [&](size_t bytes) {
-    char* p = w;
-    w += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
   const size_t nf = (size_t)B * P.nf;
   F0Out o;
-  o.freq = (double*)take(nf * F0_MAXC * 8);
-  o.str = (double*)take(nf * F0_MAXC * 8);
-  int* psi = (int*)take(nf * F0_MAXC * 4);
-  o.ncand = (int*)take(nf * 4);
-  o.inten = (double*)take(nf * 8);
-  o.cim = (int*)take(nf * F0_MAXC * 4);
   o.rw = f0_rw(P);
-  o.rwin = (double*)take(nf * (size_t)o.rw * 8);
-  o.work = (int*)take((1 + nf * (F0_MAXC - 1)) * 4);
-  double* gpart = (double*)take((size_t)B * F0_GP * 3 * 8);
+  int* psi;
+  double* gpart;
+  if (int st = ws.plan([&](Arena& a) {
+        o.freq = a.get<double>(nf * F0_MAXC);
+        o.str = a.get<double>(nf * F0_MAXC);
+        psi = a.get<int>(nf * F0_MAXC);
+        o.ncand = a.get<int>(nf);
+        o.inten = a.get<double>(nf);
+        o.cim = a.get<int>(nf * F0_MAXC);
+        o.rwin = a.get<double>(nf * (size_t)o.rw);
+        o.work = a.get<int>(1 + nf * (F0_MAXC - 1));
+        gpart = a.get<double>((size_t)B * F0_GP * 3);
+      }))
+    return st;
   // the frame pass's LDS holds r (2 bmax + 1 doubles) and the peak lists (3 x (iend + 1) / 2 + 6 words) in the FFT's
   // 2 * nfft / 2 doubles and the quarter twiddle table after it (nfft / 2 doubles, dead after the inverse FFT)
   SVC_REQUIRE((2 * P.bmax + 2) + 3 * ((std::min(P.maxlag, P.bmax) + 1) / 2 + 2) <= 3 * P.nfft / 2,

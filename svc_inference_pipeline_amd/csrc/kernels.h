@@ -5,6 +5,7 @@
 #pragma once
 #include "common.h"
 #include "amp_conv.h"
+#include "arena.h"
 #include "spectral.h"
 
 namespace svc {
@@ -71,19 +72,15 @@ int layernorm_dual(const float* x, const float* g, const float* b, float* y32, f
                    hipStream_t s, bool bf);
 int pack_qkv(const float* q, const float* k, const float* v, f16* qkv, int64_t rows, int D, float scale, hipStream_t s);
 int f0_praat_ac(const float* wav, int B, int64_t n_samples, double fs, double time_step, double floor_hz,
-                double ceiling_hz, double voicing, int T, double* f0_out, void* workspace, size_t ws_bytes,
-                const double* tables, hipStream_t s, const int64_t* n_b = nullptr, const int* T_b = nullptr,
-                StageRing* ring = nullptr);
-size_t f0_workspace_bytes(int B, int64_t n_samples, double fs, double time_step, double floor_hz);
+                double ceiling_hz, double voicing, int T, double* f0_out, Arena& ws, const double* tables,
+                hipStream_t s, const int64_t* n_b = nullptr, const int* T_b = nullptr, StageRing* ring = nullptr);
 size_t f0_table_doubles(double fs, double floor_hz);
 int f0_tables(double fs, double floor_hz, double* out);
 size_t pyin_table_doubles(double sr, double fmin, double fmax, int frame_length, int win_length, int hop);
-size_t pyin_workspace_bytes(int B, int F, double sr, double fmin, double fmax, int frame_length, int win_length,
-                            int hop);
 int pyin_tables(double sr, double fmin, double fmax, int frame_length, int win_length, int hop, double* out);
 int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, const int64_t* nvalid_host, double sr,
-            double fmin, double fmax, int frame_length, int win_length, int hop, int F, double* f0, void* ws,
-            size_t ws_bytes, const double* tables_dev, hipStream_t s);
+            double fmin, double fmax, int frame_length, int win_length, int hop, int F, double* f0, Arena& ws,
+            const double* tables_dev, hipStream_t s);
 size_t pcm16_table_bytes(int B);
 int pcm16(const float* wav, int B, int64_t S, void* table, int64_t max_nb, int sil, int64_t L, int turn_up,
           double volume_peak, int16_t* pcm, float* peak_out, int need_peak, hipStream_t s);

@@ -64,9 +64,8 @@ svc_status svc_op_conv1d(const float* x, int B, int T_in, int Cin, const float* 
   if ((st = pack_from_device(w, (size_t)Cout * Cin * k, bias, Cout, wh, bh))) return st;
   const int Cp = (int)round_up(Cin, 8);
   if ((st = pack_conv1d(c, g, wh.data(), bh.data(), Cout, Cin, k, Cp, dilation, pad, stride))) return st;
-  if ((st = c->ws.reserve(std::max((size_t)B * T_in * Cp * 2 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  WS_GET(f16, x16, (size_t)B * T_in * Cp);
+  f16* x16;
+  if ((st = c->ws.plan([&](Arena& ws) { x16 = ws.get<f16>((size_t)B * T_in * Cp); }))) return st;
   if ((st = f32_to_f16(x, Cin, x16, Cp, B * T_in, Cin, Cp, s, false))) return st;
   EpiArgs e = epi();
   e.act = act;
@@ -173,9 +172,8 @@ svc_status svc_op_conv_transpose1d(const float* x, int B, int T_in, int Cin, con
   if ((st = pack_from_device(w, (size_t)Cout * Cin * k, bias, Cout, wh, bh))) return st;
   std::vector<PackedGemm> ph;
   if ((st = pack_conv_transpose(c, ph, wh.data(), nullptr, bh.data(), Cin, Cout, k, stride, pad))) return st;
-  if ((st = c->ws.reserve(std::max((size_t)B * T_in * Cin * 2 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  WS_GET(f16, x16, (size_t)B * T_in * Cin);
+  f16* x16;
+  if ((st = c->ws.plan([&](Arena& ws) { x16 = ws.get<f16>((size_t)B * T_in * Cin); }))) return st;
   if ((st = f32_to_f16(x, Cin, x16, Cin, B * T_in, Cin, Cin, s, false))) return st;
   for (int r = 0; r < stride && !st; ++r) {
     EpiArgs e = epi();
@@ -198,9 +196,8 @@ svc_status svc_op_activation1d(const float* x, int B, int L, int C, const float*
   TuningScope tuning_scope_(&c->tune);
   hipStream_t s = (hipStream_t)stream;
   int st;
-  if ((st = c->ws.reserve(std::max((size_t)B * L * C * 2 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  WS_GET(f16, y16, (size_t)B * L * C);
+  f16* y16;
+  if ((st = c->ws.plan([&](Arena& ws) { y16 = ws.get<f16>((size_t)B * L * C); }))) return st;
   if ((st = activation1d(x, y16, B, L, C, C, al, be, f, s))) return st;
   // widen for the caller (the product path feeds the f16 tensor straight into the next conv)
   return f16_to_f32(y16, y, (int64_t)B * L * C, s);
@@ -213,9 +210,8 @@ svc_status svc_op_activation1d_x16(const void* x16, int B, int L, int C, const f
   TuningScope tuning_scope_(&c->tune);
   hipStream_t s = (hipStream_t)stream;
   int st;
-  if ((st = c->ws.reserve(std::max((size_t)B * L * C * 2 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  WS_GET(f16, y16, (size_t)B * L * C);
+  f16* y16;
+  if ((st = c->ws.plan([&](Arena& ws) { y16 = ws.get<f16>((size_t)B * L * C); }))) return st;
   if ((st = activation1d(nullptr, y16, B, L, C, C, al, be, f, s, nullptr, 1, (const f16*)x16))) return st;
   return f16_to_f32(y16, y, (int64_t)B * L * C, s);
 }
@@ -228,10 +224,12 @@ svc_status svc_op_attention(const float* q, const float* k, const float* v, int 
   hipStream_t s = (hipStream_t)stream;
   int st;
   const size_t rows = (size_t)B * L;
-  if ((st = c->ws.reserve(std::max(rows * D * 2 * 4 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  WS_GET(f16, qkv, rows * 3 * D);
-  WS_GET(f16, o16, rows * D);
+  f16 *qkv, *o16;
+  if ((st = c->ws.plan([&](Arena& ws) {
+        qkv = ws.get<f16>(rows * 3 * D);
+        o16 = ws.get<f16>(rows * D);
+      })))
+    return st;
   if ((st = pack_qkv(q, k, v, qkv, (int64_t)rows, D, powf(64.0f, -0.25f), s))) return st;
   if ((st = attention(qkv, o16, B, L, D, s, false))) return st;
   return f16_to_f32(o16, out, (int64_t)rows * D, s);
@@ -251,10 +249,12 @@ svc_status svc_op_attention_ragged(const float* q, const float* k, const float* 
   hipStream_t s = (hipStream_t)stream;
   int st;
   const size_t rows = (size_t)B * L;
-  if ((st = c->ws.reserve(std::max(rows * D * 2 * 4 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  WS_GET(f16, qkv, rows * 3 * D);
-  WS_GET(f16, o16, rows * D);
+  f16 *qkv, *o16;
+  if ((st = c->ws.plan([&](Arena& ws) {
+        qkv = ws.get<f16>(rows * 3 * D);
+        o16 = ws.get<f16>(rows * D);
+      })))
+    return st;
   RingRetire retire_(c->lens_main, s);
   void* dev = nullptr;
   if ((st = c->lens_main.put(lens, (size_t)B * sizeof(int32_t), s, &dev))) return st;

@@ -396,14 +396,6 @@ size_t pyin_table_doubles(double sr, double fmin, double fmax, int frame_length,
   return PY_NTH + 2 * (size_t)p.n_bins * (2 * p.half_width + 1) + p.n_bins;
 }
 
-size_t pyin_workspace_bytes(int B, int F, double sr, double fmin, double fmax, int frame_length, int win_length,
-                            int hop) {
-  PyinPlan p;
-  if (pyin_plan(sr, fmin, fmax, frame_length, win_length, hop, &p)) return 0;
-  const size_t fr = (size_t)B * F;
-  return fr * ((size_t)p.n_bins * 8 + 8 + 2 * (size_t)p.n_bins * 2) + 4 * 256;
-}
-
 // host tables (f64, computed as librosa computes them): beta threshold prior [100], log(transition + tiny) over the
 // band [2][n_bins][2 hw + 1], the bin frequencies [n_bins]
 int pyin_tables(double sr, double fmin, double fmax, int frame_length, int win_length, int hop, double* out) {
@@ -444,11 +436,11 @@ int pyin_tables(double sr, double fmin, double fmax, int frame_length, int win_l
 // wav f32 [B][ld]; nvalid_dev: per-utterance samples (device) or NULL; nvalid_host the same on the host (frame count
 // checks); tables_dev: pyin_tables() on the device, alive until the launches have run; f0 f64 [B][F] out
 int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, const int64_t* nvalid_host, double sr,
-            double fmin, double fmax, int frame_length, int win_length, int hop, int F, double* f0, void* ws,
-            size_t ws_bytes, const double* tables_dev, hipStream_t s) {
+            double fmin, double fmax, int frame_length, int win_length, int hop, int F, double* f0, Arena& ws,
+            const double* tables_dev, hipStream_t s) {
   PyinPlan p;
   if (int st = pyin_plan(sr, fmin, fmax, frame_length, win_length, hop, &p)) return st;
-  SVC_REQUIRE(wav && f0 && ws && tables_dev && B > 0 && ld > 0 && B <= 65535, "pyin: bad args");
+  SVC_REQUIRE(wav && f0 && tables_dev && B > 0 && ld > 0 && B <= 65535, "pyin: bad args");
   int64_t fmax_frames = 0;
   for (int b = 0; b < B; ++b) {
     const int64_t n = nvalid_host ? nvalid_host[b] : ld;
@@ -457,8 +449,6 @@ int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, cons
     fmax_frames = std::max(fmax_frames, 1 + n / hop);
   }
   SVC_REQUIRE(F >= fmax_frames && F <= (1 << 24), "pyin: %d output frames for %lld", F, (long long)fmax_frames);
-  const size_t need = pyin_workspace_bytes(B, F, sr, fmin, fmax, frame_length, win_length, hop);
-  SVC_REQUIRE(ws_bytes >= need, "pyin: workspace %zu < %zu", ws_bytes, need);
   PyinArgs a{};
   a.wav = wav;
   a.ld = ld;
@@ -482,15 +472,12 @@ int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, cons
   a.log_band = tables_dev + PY_NTH;
   a.freqs = a.log_band + 2 * (size_t)p.n_bins * (2 * p.half_width + 1);
   const size_t fr = (size_t)B * F;
-  char* q = reinterpret_cast<char*>(ws);
-  auto take = [&](size_t bytes) {
-    char* r = q;
-    q += (bytes + 255) & ~(size_t)255;
-    return r;
-  };
-  a.logobs = reinterpret_cast<double*>(take(fr * p.n_bins * 8));
-  a.logunv = reinterpret_cast<double*>(take(fr * 8));
-  a.ptr = reinterpret_cast<uint16_t*>(take(fr * 2 * p.n_bins * 2));
+  if (int st = ws.plan([&](Arena& w) {
+        a.logobs = w.get<double>(fr * p.n_bins);
+        a.logunv = w.get<double>(fr);
+        a.ptr = w.get<uint16_t>(fr * 2 * p.n_bins);
+      }))
+    return st;
   a.f0 = f0;
   const int tok = prof_begin("pyin_frame", 0.0, 0.0, s);
   hipLaunchKernelGGL(pyin_frame_kernel, dim3((unsigned)F, (unsigned)B), dim3(PY_NT), 0, s, a);

@@ -29,20 +29,21 @@ svc_status svc_bigvgan(svc_ctx* c, const float* x0, int B, int T, const int32_t*
   SVC_REQUIRE((int64_t)T * maxLC * 4 < ((int64_t)1 << 31),
               "bigvgan: T=%d frames per utterance exceeds the vocoder's limit of %lld frames (2 GiB stage span)", T,
               (long long)((((int64_t)1 << 31) - 1) / ((int64_t)maxLC * 4)));
-  const size_t big = (size_t)B * T * maxLC;
-  const size_t need = (size_t)B * T * ldm * 2 + (size_t)B * T * c->v_c0 * 2 + big * (4 * 4 + 2 * 2) + 32 * 4096;
-  int st;
-  if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
-  c->ws.reset();
   SVC_REQUIRE(T * c->hop_out >= c->nfade, "bigvgan: T=%d shorter than the fade-out", T);
-  WS_GET(f16, mel16, (size_t)B * T * ldm);
-  WS_GET(f16, pre16, (size_t)B * T * c->v_c0);
-  WS_GET(float, X, big);
-  WS_GET(float, Xj, big);
-  WS_GET(float, tmp, big);
-  WS_GET(float, XS, big);
-  WS_GET(f16, a16, big);
-  WS_GET(f16, next16, big);
+  const size_t big = (size_t)B * T * maxLC;
+  f16 *mel16, *pre16, *a16, *next16;
+  float *X, *Xj, *tmp, *XS;
+  int st = c->ws.plan([&](Arena& ws) {
+    mel16 = ws.get<f16>((size_t)B * T * ldm);
+    pre16 = ws.get<f16>((size_t)B * T * c->v_c0);
+    X = ws.get<float>(big);
+    Xj = ws.get<float>(big);
+    tmp = ws.get<float>(big);
+    XS = ws.get<float>(big);
+    a16 = ws.get<f16>(big);
+    next16 = ws.get<f16>(big);
+  });
+  if (st) return st;
   // amp_maxc: widest channel count that takes the fused kernel (0: activation1d + GEMM everywhere). C = 48 unfused is
   // 9 % slower (its N = 48 GEMMs are too narrow for the MFMA tiles); C = 96 fused is 1.0 ms per step faster than
   // activation1d + amp_conv's plain conv since both run on 256-row tiles of 2 x 2 waves (round 6; on the round-5 128-row

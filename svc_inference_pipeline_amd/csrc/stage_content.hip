@@ -28,20 +28,23 @@ static int whisper_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n,
   const int X3 = c->content_split ? 3 : 1;  // split-fp16 block operands are [hi | lo | hi] rows
   const int XS = c->content_mode != 0 ? 3 : 1;  // the conv stem is split-fp16 in both split modes
   const int LDM = XS == 3 ? c->wstem_ld : c->wmels;  // the stem operand's row stride
-  size_t need = rows1 * c->wmels * 4 + rows1 * LDM * 2 + rows1 * D * 2 * XS /*h1*/ +
-                rows2 * D * 4 + rows2 * D * 2 * X3 + rows2 * 3 * D * 2 + rows2 * D * 2 + rows2 * 4 * D * 2 * X3 + 64 * 4096;
-  if (!feats) need += rows2 * D * 4 + 4096;
-  int st;
-  if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
-  c->ws.reset();
-  if (!feats) {
-    WS_GET(float, fws, rows2 * D);
-    feats = fws;
-  }
+  float *fws = nullptr, *ls, *mx, *x;
+  f16 *lm16, *h1, *n16, *qkv, *o16, *h16;
+  int st = c->ws.plan([&](Arena& ws) {
+    if (!feats) fws = ws.get<float>(rows2 * D);
+    ls = ws.get<float>(rows1 * c->wmels);
+    lm16 = ws.get<f16>(rows1 * LDM);
+    mx = ws.get<float>(B);
+    h1 = ws.get<f16>(rows1 * D * XS);
+    x = ws.get<float>(rows2 * D);
+    n16 = ws.get<f16>(rows2 * D * X3);
+    qkv = ws.get<f16>(rows2 * 3 * D);
+    o16 = ws.get<f16>(rows2 * D);
+    h16 = ws.get<f16>(rows2 * 4 * D * X3);
+  });
+  if (st) return st;
+  if (!feats) feats = fws;
   if (feats_used) *feats_used = feats;
-  WS_GET(float, ls, rows1 * c->wmels);
-  WS_GET(f16, lm16, rows1 * LDM);
-  WS_GET(float, mx, B);
   DftArgs a{};
   a.wav = wav16;
   a.wav_stride = n;
@@ -65,14 +68,12 @@ static int whisper_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n,
   if ((st = whisper_normalize(ls, mx, lm16, B, (int64_t)F * c->wmels, s, XS == 3 ? c->wmels : 0, c->bf16, LDM)))
     return st;
   // conv stem
-  WS_GET(f16, h1, rows1 * D * XS);
   EpiArgs e = epi();
   e.act = ACT_GELU;
   e.out16 = h1;
   e.ld16 = D * XS;
   e.split16 = XS == 3 ? D : 0;
   if ((st = run_gemm(c->wconv1, lm16, LDM, LDM, B, F, F, e, s, "whisper.conv1"))) return st;
-  WS_GET(float, x, rows2 * D);
   e = epi();
   e.act = ACT_GELU;
   e.add_t = c->wpos;
@@ -80,10 +81,6 @@ static int whisper_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n,
   e.out32 = x;
   e.ld32 = D;
   if ((st = run_gemm(c->wconv2, h1, D * XS, D * XS, B, F, L, e, s, "whisper.conv2"))) return st;
-  WS_GET(f16, n16, rows2 * D * X3);
-  WS_GET(f16, qkv, rows2 * 3 * D);
-  WS_GET(f16, o16, rows2 * D);
-  WS_GET(f16, h16, rows2 * 4 * D * X3);
   const float qk_scale = powf((float)(D / c->wH), -0.25f);
   // whisper_streams = n > 1 runs the 24 blocks as utterance-aligned sub-batches on n streams (as the sampler
   // does): rows are time-major per utterance, so a sub-batch is a row range of every buffer, and one sub-batch's
@@ -294,9 +291,6 @@ static int hubert_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, 
   const int64_t R5 = cdiv64(n, 5);
   const size_t rows0 = (size_t)B * t[1], rowsF = (size_t)B * F;
   const int kChunks = 64;
-  size_t need = (size_t)B * R5 * w5 * 2 + rows0 * Cc * 4 + rows0 * Cc * 2 * X3 + (size_t)B * kChunks * Cc * 16 +
-                (size_t)B * Cc * 8 + (size_t)B * (t[2] + t[3]) * Cc * 2 * X3 + rowsF * Cc * (4 + 2 * X3) +
-                rowsF * D * (4 + 2 * X3) + rowsF * 3 * D * 2 + rowsF * D * 2 + rowsF * Fd * 2 * X3 + 32 * 4096;
   int st;
   // per-utterance tables: samples (int64 [B]), then conv_layers[0] rows t1 and frames F (int32 [B] each)
   const int64_t* nb_dev = nullptr;
@@ -321,18 +315,28 @@ static int hubert_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, 
     t1_dev = reinterpret_cast<const int*>(reinterpret_cast<char*>(dev) + (size_t)B * 8);
     F_dev = t1_dev + B;
   }
-  if ((st = c->ws.reserve(std::max(need, c->ws.cap)))) return st;
-  c->ws.reset();
+  f16 *f5, *g16, *pa, *pb, *ln16, *x16, *qkv, *o16, *h16;
+  float *c0, *c6, *x;
+  double* part;
+  float2* gss;
+  if ((st = c->ws.plan([&](Arena& ws) {
+        f5 = ws.get<f16>((size_t)B * R5 * w5);
+        c0 = ws.get<float>(rows0 * Cc);
+        g16 = ws.get<f16>(rows0 * Cc * X3);
+        part = ws.get<double>((size_t)B * kChunks * Cc * 2);
+        gss = ws.get<float2>((size_t)B * Cc);
+        pa = ws.get<f16>((size_t)B * t[2] * Cc * X3);
+        pb = ws.get<f16>((size_t)B * t[3] * Cc * X3);
+        c6 = ws.get<float>(rowsF * Cc);
+        ln16 = ws.get<f16>(rowsF * Cc * X3);
+        x = ws.get<float>(rowsF * D);
+        x16 = ws.get<f16>(rowsF * D * X3);
+        qkv = ws.get<f16>(rowsF * 3 * D);
+        o16 = ws.get<f16>(rowsF * D);
+        h16 = ws.get<f16>(rowsF * Fd * X3);
+      })))
+    return st;
   // ---- feature extractor (wav2vec2 ConvFeatureExtractionModel, mode "default")
-  WS_GET(f16, f5, (size_t)B * R5 * w5);
-  WS_GET(float, c0, rows0 * Cc);
-  WS_GET(f16, g16, rows0 * Cc * X3);
-  WS_GET(double, part, (size_t)B * kChunks * Cc * 2);
-  WS_GET(float2, gss, (size_t)B * Cc);
-  WS_GET(f16, pa, (size_t)B * t[2] * Cc * X3);
-  WS_GET(f16, pb, (size_t)B * t[3] * Cc * X3);
-  WS_GET(float, c6, rowsF * Cc);
-  WS_GET(f16, ln16, rowsF * Cc * X3);
   if ((st = hubert_frames5(wav16, B, n, f5, sp, s, c->bf16, nb_dev))) return st;
   EpiArgs e = epi();
   e.out32 = c0;
@@ -360,8 +364,6 @@ static int hubert_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, 
   if ((st = sp ? layernorm_f16x3(c6, c->hln_g, c->hln_b, ln16, (int)rowsF, Cc, s, c->bf16)
                : layernorm_f16(c6, c->hln_g, c->hln_b, ln16, (int)rowsF, Cc, Cc, s, c->bf16)))
     return st;
-  WS_GET(float, x, rowsF * D);
-  WS_GET(f16, x16, rowsF * D * X3);
   e = epi();
   e.out32 = x;
   e.ld32 = D;
@@ -387,9 +389,6 @@ static int hubert_encode_impl(svc_ctx* c, const float* wav16, int B, int64_t n, 
       return st;
   }
   if ((st = layernorm_dual(x, c->henc_ln_g, c->henc_ln_b, x, x16, (int)rowsF, D, sp, s, c->bf16))) return st;
-  WS_GET(f16, qkv, rowsF * 3 * D);
-  WS_GET(f16, o16, rowsF * D);
-  WS_GET(f16, h16, rowsF * Fd * X3);
   const float qk_scale = powf(64.0f, -0.25f);  // q * dh^-1/2 split over q and k
   for (int i = 0; i < c->hLayers; ++i) {
     HBlock& b = c->hblocks[i];
@@ -459,29 +458,6 @@ int svc_hubert_dims(svc_ctx* c, int* final_dim, int* embed_dim) {
 }
 
 // ---------------------------------------------------------------------------- conditioner
-static int condition_impl(svc_ctx* c, const void* content16, const double* f0, const float* energy,
-                          const int32_t* singer, int B, int T, float* cond, f16* cond16, hipStream_t s) {
-  const int rows = B * T;
-  WS_GET(int, im, rows);
-  WS_GET(int, ie, rows);
-  int st;
-  if ((st = bucketize(f0, energy, c->mbins, c->ebins, c->n_bins - 1, im, ie, rows, s))) return st;
-  EpiArgs e = epi();
-  e.kind = EPI_COND;
-  e.idx_m = im;
-  e.idx_l = ie;
-  e.singer = singer;
-  e.emb_m = c->emb_m;
-  e.emb_l = c->emb_l;
-  e.emb_s = c->emb_s;
-  e.ld_emb = c->C;
-  e.out32 = cond;
-  e.ld32 = c->C;
-  e.out16 = cond16;
-  e.ld16 = c->C;
-  return run_gemm(c->content_lin, (const f16*)content16, c->content_dim, c->content_dim, B, T, T, e, s, "cond.content");
-}
-
 svc_status svc_condition_indices(svc_ctx* c, const double* f0, const float* energy, int n, int32_t* melody_idx,
                                  int32_t* loudness_idx, void* stream) {
   CTX_READY(c);
@@ -495,10 +471,26 @@ svc_status svc_condition(svc_ctx* c, const void* content16, const double* f0, co
                          const int32_t* singer, int B, int T, float* cond, void* stream) {
   CTX_READY(c);
   SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
-  int st;
-  if ((st = c->ws.reserve(std::max((size_t)B * T * 8 + 4096, c->ws.cap)))) return st;
-  c->ws.reset();
-  return condition_impl(c, content16, f0, energy, singer, B, T, cond, nullptr, (hipStream_t)stream);
+  hipStream_t s = (hipStream_t)stream;
+  const int rows = B * T;
+  int *im, *ie;
+  int st = c->ws.plan([&](Arena& ws) {
+    im = ws.get<int>(rows);
+    ie = ws.get<int>(rows);
+  });
+  if (st || (st = bucketize(f0, energy, c->mbins, c->ebins, c->n_bins - 1, im, ie, rows, s))) return st;
+  EpiArgs e = epi();
+  e.kind = EPI_COND;
+  e.idx_m = im;
+  e.idx_l = ie;
+  e.singer = singer;
+  e.emb_m = c->emb_m;
+  e.emb_l = c->emb_l;
+  e.emb_s = c->emb_s;
+  e.ld_emb = c->C;
+  e.out32 = cond;
+  e.ld32 = c->C;
+  return run_gemm(c->content_lin, (const f16*)content16, c->content_dim, c->content_dim, B, T, T, e, s, "cond.content");
 }
 
 }  // extern "C"

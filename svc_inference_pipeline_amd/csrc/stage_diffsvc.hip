@@ -16,6 +16,7 @@ struct DenoiseBufs {
   size_t g_ls;   // elements between layers of g16, also layer-major [NL][rows_total][C]: the gate GEMM writes and the
                  // residual GEMM reads one contiguous block; the skip GEMM reads the NL blocks as NL "taps" whose row
                  // shift is the layer stride (tap_mul = rows_total)
+  f16* cond16;   // [rows][3C] the conditioner output as the [hi | lo | hi] operand of the projections (project_cond)
 };
 
 
@@ -120,28 +121,24 @@ static int denoise(svc_ctx* c, const DenoiseBufs& bb, const f16* x16, int B, int
   return plms ? plms_update(*plms, rows, c->n_mel, s) : SVC_OK;
 }
 
-static int alloc_denoise(svc_ctx* c, int B, int T, DenoiseBufs& bb) {
+// the denoiser's part of a workspace layout (the sampler's, svc_diffsvc_eps's): gets only
+static void layout_denoise(svc_ctx* c, Arena& ws, int B, int T, DenoiseBufs& bb) {
   const size_t rows = (size_t)B * T, C = c->C;
-  WS_GET(f16, cp16, rows * c->n_layers * 2 * C);
-  WS_GET(f16, y16, rows * C);
-  WS_GET(f16, g16, rows * c->n_layers * C);
-  WS_GET(f16, s16, rows * C * 3);  // [hi | lo | hi] when head_split
-  WS_GET(f16, u16, rows * C * 3);
-  WS_GET(f16, lo16, rows * C);
-  bb = DenoiseBufs{cp16, y16, g16, s16, u16, lo16, rows * 2 * C, rows * C};
-  return SVC_OK;
-}
-
-static size_t denoise_bytes(svc_ctx* c, int B, int T) {
-  const size_t rows = (size_t)B * T, C = c->C;
-  return rows * c->n_layers * 2 * C * 2 + rows * c->n_layers * C * 2 + rows * C * 2 * 9 + 26 * 4096;
+  bb.cp16 = ws.get<f16>(rows * c->n_layers * 2 * C);
+  bb.y16 = ws.get<f16>(rows * C);
+  bb.g16 = ws.get<f16>(rows * c->n_layers * C);
+  bb.s16 = ws.get<f16>(rows * C * 3);  // [hi | lo | hi] when head_split
+  bb.u16 = ws.get<f16>(rows * C * 3);
+  bb.lo16 = ws.get<f16>(rows * C);
+  bb.cp_ls = rows * 2 * C;
+  bb.g_ls = rows * C;
+  bb.cond16 = ws.get<f16>(rows * 3 * C);
 }
 
 static int project_cond(svc_ctx* c, const float* cond, int B, int T, const DenoiseBufs& bb, hipStream_t s) {
   const int rows = B * T, C = c->C;
-  WS_GET(f16, cond16, (size_t)rows * 3 * C);
   int st;
-  if ((st = f32_to_f16x3(cond, C, cond16, rows, C, s, c->bf16))) return st;  // [hi | lo | hi] split-fp16 operand
+  if ((st = f32_to_f16x3(cond, C, bb.cond16, rows, C, s, c->bf16))) return st;  // [hi | lo | hi] split-fp16 operand
   // the projections of all layers as ONE GEMM over the packed weights (N = NL x 2C), each layer's 2C columns written
   // to its layer-major cp block (EpiArgs col_block): 20 launches of 470 tiles (1.8 rounds of workgroups each) became
   // one launch of 9 400 (round 5)
@@ -150,7 +147,7 @@ static int project_cond(svc_ctx* c, const float* cond, int B, int T, const Denoi
   e.ld16 = 2 * C;
   e.col_block = 2 * C;
   e.col_block_stride = (int64_t)bb.cp_ls;
-  if ((st = run_gemm(c->cp_all, cond16, 3 * C, 3 * C, B, T, T, e, s, "diffsvc.condproj"))) return st;
+  if ((st = run_gemm(c->cp_all, bb.cond16, 3 * C, 3 * C, B, T, T, e, s, "diffsvc.condproj"))) return st;
   return SVC_OK;
 }
 
@@ -181,15 +178,19 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
   SVC_REQUIRE(mode != SVC_MODE_DDPM || noise || utt_ids, "sample: DDPM without `noise` needs utt_ids");
   hipStream_t s = (hipStream_t)stream;
   const int rows = B * T, nm = c->n_mel, ld16 = (int)round_up(nm, 8);
-  int st;
-  const size_t extra = (size_t)rows * (ld16 * 2 * 2 + nm * 4 * 8 + c->C * 6) + 32 * 4096;
-  if ((st = c->ws.reserve(std::max(denoise_bytes(c, B, T) + extra, c->ws.cap)))) return st;
-  c->ws.reset();
   DenoiseBufs bb;
-  if ((st = alloc_denoise(c, B, T, bb))) return st;
-  if ((st = project_cond(c, cond, B, T, bb, s))) return st;
+  f16 *x16, *xp16;
+  float *eps, *hist[5], *xp;
+  int st = c->ws.plan([&](Arena& ws) {
+    layout_denoise(c, ws, B, T, bb);
+    x16 = ws.get<f16>((size_t)rows * ld16);
+    eps = ws.get<float>((size_t)rows * nm);
+    for (int k = 0; k < 5; ++k) hist[k] = ws.get<float>((size_t)rows * nm);
+    xp = ws.get<float>((size_t)rows * nm);
+    xp16 = ws.get<f16>((size_t)rows * ld16);
+  });
+  if (st || (st = project_cond(c, cond, B, T, bb, s))) return st;
   float* x = x0;  // the sampler state lives in the output buffer
-  WS_GET(f16, x16, (size_t)rows * ld16);
   SVC_HIP_CHECK(hipMemsetAsync(x16, 0, (size_t)rows * ld16 * sizeof(f16), s));  // zero pad channels
   if (x_T) {
     SVC_HIP_CHECK(hipMemcpyAsync(x, x_T, (size_t)rows * nm * 4, hipMemcpyDeviceToDevice, s));
@@ -197,14 +198,6 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
   } else {
     if ((st = init_noise(x, x16, ld16, B, T, nm, seed, utt_ids, 1.0f / 1.2f, s, c->bf16))) return st;
   }
-  WS_GET(float, eps, (size_t)rows * nm);
-  float* hist[5];
-  for (int k = 0; k < 5; ++k) {
-    WS_GET(float, hb, (size_t)rows * nm);
-    hist[k] = hb;
-  }
-  WS_GET(float, xp, (size_t)rows * nm);
-  WS_GET(f16, xp16, (size_t)rows * ld16);
   SVC_HIP_CHECK(hipMemsetAsync(xp16, 0, (size_t)rows * ld16 * sizeof(f16), s));
 
   // Utterance-aligned sub-batches on their own streams, issued kernel by kernel in alternation: their
@@ -352,14 +345,13 @@ svc_status svc_diffsvc_eps(svc_ctx* c, const float* cond, const float* x, int B,
   RingRetire retire_(c->lens_main, s);
   if (int st0 = stage_frames(c->lens_main, frames, B, T, s, &tv)) return st0;
   const int rows = B * T, ld16 = (int)round_up(c->n_mel, 8);
-  int st;
-  if ((st = c->ws.reserve(std::max(denoise_bytes(c, B, T) + (size_t)rows * (ld16 * 2 + c->C * 6) + 8192, c->ws.cap))))
-    return st;
-  c->ws.reset();
   DenoiseBufs bb;
-  if ((st = alloc_denoise(c, B, T, bb))) return st;
-  if ((st = project_cond(c, cond, B, T, bb, s))) return st;
-  WS_GET(f16, x16, (size_t)rows * ld16);
+  f16* x16;
+  int st = c->ws.plan([&](Arena& ws) {
+    layout_denoise(c, ws, B, T, bb);
+    x16 = ws.get<f16>((size_t)rows * ld16);
+  });
+  if (st || (st = project_cond(c, cond, B, T, bb, s))) return st;
   if ((st = f32_to_f16(x, c->n_mel, x16, ld16, rows, c->n_mel, ld16, s, c->bf16))) return st;
   if ((st = denoise(c, bb, x16, B, T, t, eps, s, tv))) return st;
   return tv ? zero_tail_rows(eps, B, T, c->n_mel, tv, s) : SVC_OK;

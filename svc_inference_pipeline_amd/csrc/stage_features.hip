@@ -84,9 +84,7 @@ svc_status svc_f0_ac(svc_ctx* c, const float* wav, int B, int64_t n, const int64
                      void* stream) {
   CTX_READY(c);
   const double ts = (double)c->hop / c->fs;
-  size_t need = f0_workspace_bytes(B, n, c->fs, ts, c->f0_min);
   int st;
-  if ((st = c->auxws.reserve(std::max(need + 4096, c->auxws.cap)))) return st;
   std::vector<int> Tb;
   if (n_samples) {
     Tb.resize(B);
@@ -106,8 +104,8 @@ svc_status svc_f0_ac(svc_ctx* c, const float* wav, int B, int64_t n, const int64
     if ((st = c->f0_tabs.insert(key, 2, f0_tab))) return st;
   }
   RingRetire retire_(c->lens_feat, (hipStream_t)stream);
-  return f0_praat_ac(wav, B, n, c->fs, ts, c->f0_min, c->f0_max, 0.6, T, f0, c->auxws.base, c->auxws.cap, f0_tab,
-                     (hipStream_t)stream, n_samples, n_samples ? Tb.data() : nullptr, &c->lens_feat);
+  return f0_praat_ac(wav, B, n, c->fs, ts, c->f0_min, c->f0_max, 0.6, T, f0, c->auxws, f0_tab, (hipStream_t)stream,
+                     n_samples, n_samples ? Tb.data() : nullptr, &c->lens_feat);
 }
 
 svc_status svc_f0_pyin(svc_ctx* c, const float* wav, int B, int64_t n, const int64_t* n_samples, double fs,
@@ -119,9 +117,7 @@ svc_status svc_f0_pyin(svc_ctx* c, const float* wav, int B, int64_t n, const int
   const size_t nt = pyin_table_doubles(fs, f0_min, f0_max, FL, win_length, hop_length);
   if (!nt) return SVC_ERR_INVALID;  // (pyin_plan set the error)
   SVC_REQUIRE(B > 0 && n > 0 && T > 0, "pyin: B=%d n=%lld T=%d", B, (long long)n, T);
-  const size_t need = pyin_workspace_bytes(B, T, fs, f0_min, f0_max, FL, win_length, hop_length);
   int st;
-  if ((st = c->auxws.reserve(std::max(need + 4096, c->auxws.cap)))) return st;
   // the tables depend only on (fs, f0_min, f0_max, win, hop): built and uploaded once per parameter set
   const double key[5] = {fs, f0_min, f0_max, (double)win_length, (double)hop_length};
   double* pyin_tab = c->pyin_tabs.find(key, 5);
@@ -145,8 +141,8 @@ svc_status svc_f0_pyin(svc_ctx* c, const float* wav, int B, int64_t n, const int
     if ((st = c->lens_feat.put(n_samples, (size_t)B * 8, s, &dev))) return st;
     nb_dev = reinterpret_cast<const int64_t*>(dev);
   }
-  return f0_pyin(wav, B, n, nb_dev, n_samples, fs, f0_min, f0_max, FL, win_length, hop_length, T, f0, c->auxws.base,
-                 c->auxws.cap, pyin_tab, s);
+  return f0_pyin(wav, B, n, nb_dev, n_samples, fs, f0_min, f0_max, FL, win_length, hop_length, T, f0, c->auxws,
+                 pyin_tab, s);
 }
 
 svc_status svc_pitch_shift(svc_ctx* c, double* f0, int B, int T, double target_median, void* stream) {
