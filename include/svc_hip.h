@@ -7,6 +7,8 @@
  *   svc_mel_energy      <- utils/mel.py:179-201 extract_mel_features (mel_spectrogram :130-174, energy :199)
  *   svc_f0_ac           <- utils/f0.py:120-161 get_f0_features_using_parselmouth (Praat to_pitch_ac + pad)
  *   svc_pitch_shift     <- utils/acoustic_feature_extraction.py:48-52 pitch_shift
+ *   svc_pitch_shift_ex  <- the same with a target median (and an optional key scale) per utterance
+ *   svc_f0_voiced_median <- utils/acoustic_feature_extraction.py:21-30 get_target_f0_median (a singer's pooled contours)
  *   svc_whisper_encode  <- utils/whisper.py:13-28 whisper_encoder (log_mel_spectrogram + AudioEncoder)
  *   svc_map_content     <- utils/whisper.py:31-81 get_mapped_whisper_features
  *   svc_whisper_content_ragged <- utils/whisper.py:13-81, both of the above for a ragged batch: every 30 s window that
@@ -127,6 +129,25 @@ svc_status svc_f0_pyin(svc_ctx* ctx, const float* wav, int B, int64_t n_samples,
 /* A4: in place, f0 [B*T] float64 *= target_median / median(voiced f0 of that utterance)
    (utils/acoustic_feature_extraction.py:33-52; np.median semantics, NaN when no frame is voiced). */
 svc_status svc_pitch_shift(svc_ctx* ctx, double* f0, int B, int T, double target_median, void* stream);
+
+/* A4 with a target per utterance. Row b: f0[b, :] *= target_median[b] / median(voiced f0[b, :]), then * scale[b] where
+   scale is given: factor = target_median[b] / med; factor = factor * scale[b]; f0 *= factor, in that order (f64).
+   target_median, scale: HOST f64 [B] (scale NULL = none); each must be finite and > 0 (checked before any device call,
+   SVC_ERR_INVALID otherwise). With scale NULL and equal targets the result is bit-identical to svc_pitch_shift. The
+   tables are staged through the feature stages' ring, like the ragged-batch lengths. */
+svc_status svc_pitch_shift_ex(svc_ctx* ctx, double* f0, int B, int T, const double* target_median,
+                              const double* scale, void* stream);
+
+/* A4, the target side: np.median of every f0[b, t] != 0 with t < frames[b] (frames: host int32 [B], NULL = all T),
+   pooled over the batch: utils/acoustic_feature_extraction.py:21-30. median: device f64 [1] (NaN where nothing is
+   voiced, as np.median of an empty selection); voiced: device int64 [1] or NULL, the pooled voiced count.
+   Stream-ordered, no host sync: a radix select in 8-bit digits on one workgroup per 2048 cells, 10 stream operations
+   per call whatever the size, integer atomics only (the same bits on every run). Requires B > 0, T > 0,
+   B * T < 2^31 and 0 <= frames[b] <= T (checked before any device call). f0 is raw extractor output and is taken to
+   be NaN-free: a NaN cell counts as voiced and sorts by its bit pattern (past +inf or before -inf), not as np.median
+   would propagate it. Uses the feature-stage workspace, like svc_f0_ac; the context need not be finalized. */
+svc_status svc_f0_voiced_median(svc_ctx* ctx, const double* f0, int B, int T, const int32_t* frames, double* median,
+                                int64_t* voiced, void* stream);
 
 /* A5+A6: wav16k [B][n_samples] f32 (int16-quantised, <= 480000 samples; zero-padded to 30 s)
    -> Whisper encoder output feats [B*n_ctx][n_state] f32.

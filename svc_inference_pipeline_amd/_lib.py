@@ -28,6 +28,8 @@ PROTOTYPES = {
     "svc_f0_pyin": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_double, c_int, c_int, c_double, c_double,
                             c_int, c_void_p, c_void_p]),
     "svc_pitch_shift": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p]),
+    "svc_pitch_shift_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "svc_f0_voiced_median": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svc_whisper_encode": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "svc_map_content": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "svc_map_content_ex": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),

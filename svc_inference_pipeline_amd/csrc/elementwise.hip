@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "median.h"
 
 namespace svc {
 
@@ -640,12 +641,7 @@ namespace svc {
 // ============================================================================ pitch shift
 // utils/acoustic_feature_extraction.py:33-52: factor = target_median / median(voiced f0); f0 *= factor.
 // The median of the voiced frames (np.median: middle element, or the mean of the two middle ones)
-// is found with a 64-pass radix select over order-preserving integer keys; one workgroup per utterance.
-__device__ __forceinline__ uint64_t dkey(double v) {
-  uint64_t b = (uint64_t)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
+// is found with a 64-pass radix select over order-preserving integer keys (dkey, median.h); one workgroup per utterance.
 __device__ double block_select(const double* f, int T, int k, int* red) {
   uint64_t prefix = 0, mask = 0;
   for (int bit = 63; bit >= 0; --bit) {
@@ -703,5 +699,54 @@ int pitch_shift(double* f0, int B, int T, double target, hipStream_t s) {
   hipLaunchKernelGGL(pitch_shift_kernel, dim3(B), dim3(256), 0, s, f0, T, target);
   SVC_LAUNCH_CHECK();
   return SVC_OK;
+}
+
+// A target per utterance (svc_pitch_shift_ex): pitch_shift_kernel's select and arithmetic with row b's own target and,
+// where given, scale: factor = target[b] / med; factor = factor * scale[b]; f0 *= factor, in that order.
+__global__ __launch_bounds__(256) void pitch_shift_ex_kernel(double* f0, int T, const double* __restrict__ target,
+                                                             const double* __restrict__ scale) {
+  __shared__ int red[4];
+  double* f = f0 + (int64_t)blockIdx.x * T;
+  int n = 0;
+  for (int i = threadIdx.x; i < T; i += blockDim.x) n += f[i] != 0.0;
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
+  __syncthreads();
+  n = red[0] + red[1] + red[2] + red[3];
+  __syncthreads();
+  double med;
+  if (n == 0) {
+    med = __longlong_as_double(0x7FF8000000000000ll);
+  } else if (n & 1) {
+    med = block_select(f, T, n / 2, red);
+  } else {
+    double a = block_select(f, T, n / 2 - 1, red);
+    double b = block_select(f, T, n / 2, red);
+    med = (a + b) / 2.0;
+  }
+  double factor = target[blockIdx.x] / med;
+  if (scale) factor = factor * scale[blockIdx.x];
+  __syncthreads();
+  for (int i = threadIdx.x; i < T; i += blockDim.x) f[i] = f[i] * factor;
+}
+
+int pitch_shift_ex(double* f0, int B, int T, const double* target, const double* scale, hipStream_t s) {
+  hipLaunchKernelGGL(pitch_shift_ex_kernel, dim3(B), dim3(256), 0, s, f0, T, target, scale);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
+// svc_f0_voiced_median: the select of median.h in its measured counting form, its histograms and state in the
+// feature stages' workspace
+int f0_voiced_median(const double* f0, int B, int T, const int* frames_dev, double* median, long long* voiced,
+                     Arena& ws, hipStream_t s) {
+  uint32_t* hist = nullptr;
+  MedianState* state = nullptr;
+  if (int st = ws.plan([&](Arena& w) {
+        hist = w.get<uint32_t>(kMedianHistWords);
+        state = w.get<MedianState>(kMedianPasses + 1);
+      }))
+    return st;
+  return median_enqueue<kMedianRounds>(f0, B, T, frames_dev, hist, state, median, voiced, s);
 }
 }  // namespace svc

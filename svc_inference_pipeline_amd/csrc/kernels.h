@@ -56,6 +56,12 @@ int diff_head(const f16* s16, const f16* Wsp, const float* bsp, int Nsp, int Ksp
               int Nout, int Kout, int Npad_out, float* eps, int ld_eps, int M, const f16* zpage, hipStream_t s,
               bool bf16);
 int pitch_shift(double* f0, int B, int T, double target, hipStream_t s);
+// target, scale: device f64 [B] (scale NULL: none)
+int pitch_shift_ex(double* f0, int B, int T, const double* target, const double* scale, hipStream_t s);
+// the pooled voiced median (median.h). frames_dev: device int32 [B] or NULL; median: device f64 [1]; voiced: device
+// int64 [1] or NULL
+int f0_voiced_median(const double* f0, int B, int T, const int* frames_dev, double* median, long long* voiced,
+                     Arena& ws, hipStream_t s);
 int content_map_hubert(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,
                        hipStream_t s, bool bf);
 int content_map_ragged(const float* src, int B, int src_rows, int ld_src, int T, int D, f16* dst, int ld_dst,

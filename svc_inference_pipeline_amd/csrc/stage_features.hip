@@ -151,6 +151,54 @@ svc_status svc_pitch_shift(svc_ctx* c, double* f0, int B, int T, double target_m
   return pitch_shift(f0, B, T, target_median, (hipStream_t)stream);
 }
 
+svc_status svc_pitch_shift_ex(svc_ctx* c, double* f0, int B, int T, const double* target_median, const double* scale,
+                              void* stream) {
+  SVC_REQUIRE(c, "pitch_shift_ex: null context");
+  SVC_REQUIRE(f0 && target_median && B > 0 && T > 0, "pitch_shift_ex: bad args (B=%d T=%d)", B, T);
+  // one staged table: f64 target[B], then f64 scale[B] where given; checked before any HIP call
+  const int cols = scale ? 2 : 1;
+  std::vector<double> tab((size_t)B * cols);
+  for (int b = 0; b < B; ++b) {
+    SVC_REQUIRE(std::isfinite(target_median[b]) && target_median[b] > 0.0,
+                "pitch_shift_ex: utterance %d: target median %g (must be finite and positive)", b, target_median[b]);
+    tab[b] = target_median[b];
+    if (scale) {
+      SVC_REQUIRE(std::isfinite(scale[b]) && scale[b] > 0.0,
+                  "pitch_shift_ex: utterance %d: scale %g (must be finite and positive)", b, scale[b]);
+      tab[(size_t)B + b] = scale[b];
+    }
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_feat, s);
+  void* dev = nullptr;
+  if (int st = c->lens_feat.put(tab.data(), tab.size() * sizeof(double), s, &dev)) return st;
+  const double* td = reinterpret_cast<const double*>(dev);
+  return pitch_shift_ex(f0, B, T, td, scale ? td + B : nullptr, s);
+}
+
+svc_status svc_f0_voiced_median(svc_ctx* c, const double* f0, int B, int T, const int32_t* frames, double* median,
+                                int64_t* voiced, void* stream) {
+  SVC_REQUIRE(c, "f0_voiced_median: null context");
+  SVC_REQUIRE(f0 && median && B > 0 && T > 0, "f0_voiced_median: bad args (B=%d T=%d)", B, T);
+  SVC_REQUIRE((int64_t)B * T < (1ll << 31), "f0_voiced_median: B * T = %lld cells (must be below 2^31)",
+              (long long)B * T);
+  if (frames)
+    for (int b = 0; b < B; ++b)
+      SVC_REQUIRE(frames[b] >= 0 && frames[b] <= T, "f0_voiced_median: utterance %d: %d frames (row length %d)", b,
+                  frames[b], T);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_feat, s);
+  const int* frames_dev = nullptr;
+  if (frames) {
+    void* dev = nullptr;
+    if (int st = c->lens_feat.put(frames, (size_t)B * sizeof(int32_t), s, &dev)) return st;
+    frames_dev = reinterpret_cast<const int*>(dev);
+  }
+  return f0_voiced_median(f0, B, T, frames_dev, median, reinterpret_cast<long long*>(voiced), c->auxws, s);
+}
+
 // ---------------------------------------------------------------------------- 16-bit PCM (A16)
 svc_status svc_pcm16(svc_ctx* c, const float* wav, int B, int64_t S, const int64_t* utt_samples, int fs,
                      int add_silence, int turn_up, double volume_peak, void* pcm, float* peak_out, void* stream) {

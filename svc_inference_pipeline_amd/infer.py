@@ -4,6 +4,9 @@ converted wav, on one MI355X through libsvc_hip.so.
     python -m svc_inference_pipeline_amd.infer --wav test_set/1100000814.wav --singer svcc_CDF1 \\
         --mapper-ckpt mapper.pt --vocoder-ckpt vocoder.pt --whisper-ckpt medium.pt [--fast] [--out gen/x.wav]
     python -m svc_inference_pipeline_amd.infer --wav a.wav b.wav c.wav ...   # several files: one ragged batch
+    python -m svc_inference_pipeline_amd.infer --singer-f0 f0.json --singer svcc_CDF1 --enroll r1.wav r2.wav ...
+        # measure the singer's voiced F0 median from the singer's own recordings and keep it in f0.json
+    python -m svc_inference_pipeline_amd.infer --singer-f0 f0.json --key 2 --wav a.wav ...   # use it; 2 semitones up
 
 Same sequence as the reference: acoustic features (mel, energy, Praat F0) -> pitch shift to the target
 singer -> Whisper (and / or ContentVec, --hubert-ckpt) content features -> DiffSVC sampler (DDPM-1000 by default, PLMS with --fast, as
@@ -25,6 +28,7 @@ from . import config as C
 from . import weights as W
 from .pipeline import SVCPipeline, hubert_content_type, wants_float16k
 from .runtime import SVCEngine
+from .singers import SingerF0Table
 
 
 def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckpt=None, random_weights=None, seed=0,
@@ -66,7 +70,7 @@ def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckp
 
 
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                 f0_method="parselmouth", pcm16=False):
+                 f0_method="parselmouth", pcm16=False, key_shift=0.0):
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
     the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16)."""
     # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
@@ -83,12 +87,12 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
     res = SVCPipeline(engine, f0_method=f0_method).convert(wav24[None].contiguous(), wav16[None].contiguous(), singer,
                                       fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=utt,
                                       wav16_float=None if wav16f is None else wav16f[None].contiguous(),
-                                      pcm16=pcm16)
+                                      pcm16=pcm16, key_shift=key_shift)
     return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                  f0_method="parselmouth", pcm16=False):
+                  f0_method="parselmouth", pcm16=False, key_shift=0.0):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
     list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
     pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
@@ -102,16 +106,26 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
         w24, w16 = A.load_batch(list(wav_paths), cfg.fs, engine)
     sid = int(singers[singer_name])
     wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), wavs16_float=w16f,
-                                            fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16)
+                                            fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16,
+                                            key_shift=key_shift)
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
     return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--wav", required=True, nargs="+",
-                    help="one or more source files; several are converted as one ragged GPU batch")
+    ap.add_argument("--wav", default=None, nargs="+",
+                    help="one or more source files; several are converted as one ragged GPU batch (may be left out "
+                         "with --enroll)")
+    ap.add_argument("--singer-f0", default=None, metavar="FILE",
+                    help="per-singer F0 medians (JSON, singers.SingerF0Table): loaded when the file exists, and saved "
+                         "after an enrolment")
+    ap.add_argument("--enroll", default=None, nargs="+", metavar="WAV",
+                    help="recordings of --singer: their voiced F0 median becomes that singer's pitch target; exits "
+                         "after the enrolment when no --wav is given")
+    ap.add_argument("--key", type=float, default=0.0, metavar="SEMITONES",
+                    help="key shift on top of the shift to the singer's median")
     ap.add_argument("--singer", default="svcc_CDF1")
     ap.add_argument("--out", default=None, help="default gen/<wav stem>_<singer>.wav (infer.py:28); one file only")
     ap.add_argument("--config", default=None, help="reference-format config.json (default: the packaged one)")
@@ -129,7 +143,26 @@ def main(argv=None):
     ap.add_argument("--f0-method", default="parselmouth", choices=("parselmouth", "pyin"),
                     help="F0 extractor: Praat AC (the reference's infer.py) or pYIN (utils/f0.py:95-117; follows "
                          "librosa 0.10.1's pyin, parity-unpinned: librosa is not installed here)")
+    return ap
+
+
+def enroll_singer(engine, cfg, singer_name, wav_paths, f0_method="parselmouth", table_path=None):
+    """--enroll: SVCPipeline.enroll of the named singer from wav files -> the table entry; the table is saved to
+    table_path where given."""
+    singers = C.load_singers(cfg)
+    if singer_name not in singers:
+        raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
+    entry = SVCPipeline(engine, f0_method=f0_method).enroll(int(singers[singer_name]), sources=list(wav_paths))
+    if table_path:
+        engine.singer_f0.save(table_path)
+    return entry
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if not args.wav and not args.enroll:
+        ap.error("need --wav (files to convert) or --enroll (recordings of --singer)")
 
     cfg = C.load_config(args.config) if args.config else C.load_config()
     mapper = args.mapper_ckpt or getattr(cfg, "svc_model_path", None)
@@ -138,6 +171,15 @@ def main(argv=None):
     hubert = args.hubert_ckpt or getattr(cfg, "contentVec_model", None)
     engine = build_engine(cfg, args.device, mapper, vocoder, args.whisper_ckpt, args.random_weights, args.seed,
                           hubert_ckpt=hubert)
+    if args.singer_f0 and os.path.exists(args.singer_f0):
+        engine.singer_f0 = SingerF0Table.load(args.singer_f0)
+    if args.enroll:
+        ent = enroll_singer(engine, cfg, args.singer, args.enroll, args.f0_method, args.singer_f0)
+        print(f"Enrolled {args.singer}: voiced F0 median {ent['median']:.3f} Hz over {ent['voiced']} voiced of "
+              f"{ent['frames']} frames, {ent['n_utts']} file(s)", flush=True)
+        if not args.wav:
+            engine.close()
+            return 0
     if args.out and len(args.wav) > 1:
         raise SystemExit("--out names one output file: omit it when converting several files")
     t0 = time.time()
@@ -145,10 +187,10 @@ def main(argv=None):
     dev = f"cuda:{args.device}"
     if len(args.wav) == 1:
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
-                                f0_method=args.f0_method, pcm16=True)]
+                                f0_method=args.f0_method, pcm16=True, key_shift=args.key)]
     else:
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
-                                f0_method=args.f0_method, pcm16=True)
+                                f0_method=args.f0_method, pcm16=True, key_shift=args.key)
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
     for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU

@@ -1,7 +1,9 @@
 """Batched counterpart of the reference's infer.py (infer.py:44-90), on one GPU.
 
     mel, energy = acoutic_feature_extractor(...)        infer.py:53   -> SVCEngine.mel_energy + f0
-    f0 = pitch_shift(f0, cfg)                           infer.py:59   -> SVCEngine.pitch_shift
+    f0 = pitch_shift(f0, cfg)                           infer.py:59   -> SVCEngine.pitch_shift (the target median per
+                                                                         clip: its singer's, once enrolled with
+                                                                         SVCPipeline.enroll; a key shift on request)
     whisper_feature = whisper_feature_extractor(...)    infer.py:64   -> whisper_encode + map_content
     contentVec_feature = contentVec_feature_extractor   infer.py:65   -> hubert_encode + map_content(rule="hubert")
     y_pred = svc_model_inference(...)                   infer.py:79   -> condition + diffsvc_sample
@@ -103,6 +105,60 @@ class SVCPipeline:
                 f0[b, tb:] = 0
         return f0
 
+    def shift_f0(self, f0, singers, key_shift=0.0):
+        """A4 on f0 f64 [B, T], in place: clip b's voiced median moves onto its singer's (engine.singer_f0; the global
+        target_f0_median for a singer that is not enrolled), then up by key_shift semitones (a scalar or one per clip;
+        the factor 2 ** (k / 12) is computed here in f64). With an empty table and no shift this is the scalar call
+        svc_pitch_shift as before, and `singers` (which may be a device tensor) is not looked at."""
+        e = self.engine
+        B = f0.shape[0]
+        table = getattr(e, "singer_f0", None)
+        ks = key_shift.tolist() if hasattr(key_shift, "tolist") else key_shift
+        ks = [float(k) for k in ks] if isinstance(ks, (list, tuple)) else [float(ks)] * B
+        if len(ks) != B:
+            raise ValueError(f"{len(ks)} key shifts for a batch of {B}")
+        if not table and not any(ks):
+            return e.pitch_shift(f0)
+        ids = singers.reshape(-1).tolist() if hasattr(singers, "tolist") else list(singers)
+        if len(ids) != B:
+            raise ValueError(f"{len(ids)} singers for a batch of {B}")
+        targets = [table.get(s, e.target_f0_median) if table else e.target_f0_median for s in ids]
+        scale = [2.0 ** (k / 12.0) for k in ks] if any(ks) else None
+        return e.pitch_shift(f0, targets, scale)
+
+    def enroll(self, singer, sources=None, wavs24=None, max_batch=16):
+        """Measure a singer's voiced F0 median from that singer's own recordings and record it as the singer's pitch
+        target (utils/acoustic_feature_extraction.py:21-30 on the GPU): wav files (`sources`: paths, bytes or
+        memoryviews, decoded by audio.load_batch) or 24 kHz f32 device tensors (`wavs24`), in ragged chunks of at most
+        max_batch clips through the configured F0 extractor; each clip's own frames are gathered into one flat buffer
+        and ONE svc_f0_voiced_median call takes the median of its voiced cells. -> the table entry {median, voiced,
+        frames, n_utts} now in engine.singer_f0. A singer without a voiced frame is a ValueError; nothing is stored."""
+        e = self.engine
+        if (sources is None) == (wavs24 is None):
+            raise ValueError("enroll: give either sources (wav files) or wavs24 (24 kHz tensors)")
+        if max_batch < 1:
+            raise ValueError("enroll: max_batch >= 1")
+        with e.lock:
+            if sources is not None:
+                from . import audio as A
+                wavs24 = A.load_batch(list(sources), e.cfg.fs, e)[0]
+            wavs24 = [w.reshape(-1) for w in wavs24]
+            if not wavs24:
+                raise ValueError("enroll: no recordings")
+            rows = []
+            for i in range(0, len(wavs24), int(max_batch)):
+                w24, n24 = self._pad_stack(wavs24[i:i + int(max_batch)])
+                T_b = [mel_frames(k, e.cfg.n_fft, e.cfg.hop_length) for k in n24]
+                f0 = self.extract_f0(w24, max(T_b), n_samples=n24, T_b=T_b)
+                rows += [f0[b, :tb] for b, tb in enumerate(T_b)]
+            flat = torch.cat(rows).to(torch.float64).contiguous()
+            med, cnt = e.f0_voiced_median(flat)
+            voiced = int(cnt.item())
+            if voiced == 0:
+                raise ValueError(f"enroll: singer {singer}: no voiced frame in {len(wavs24)} recording(s)")
+            return e.singer_f0.set(singer, float(med.item()), voiced=voiced, frames=int(flat.numel()),
+                                   n_utts=len(wavs24))
+
     def content(self, wav16, T, wav16_float=None):
         """Content features of every type in cfg.mapper.content_feature mapped to T mel frames -> [B, T, sum of
         widths] in the engine's content_dtype (f16, or bf16 with operands="bf16"), the types' columns concatenated in ascending name order (the order in which the
@@ -155,16 +211,17 @@ class SVCPipeline:
         return self._side
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
-                noise=None, f0=None, wav16_float=None, pcm16=False):
+                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
         Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
-        save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`."""
+        save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`.
+        key_shift: semitones on top of the shift to the singer's median, a scalar or one per clip (shift_f0)."""
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
-                                 wav16_float, pcm16)
+                                 wav16_float, pcm16, key_shift)
 
     def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
-                 pcm16=False):
+                 pcm16=False, key_shift=0.0):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -177,7 +234,7 @@ class SVCPipeline:
             mel, energy = e.mel_energy(wav24)
             # a caller-supplied f0 is shifted on a copy (svc_pitch_shift works in place)
             f0 = self.extract_f0(wav24, T) if f0 is None else f0.to(torch.float64).contiguous().clone()
-            e.pitch_shift(f0)
+            self.shift_f0(f0, singer, key_shift)
         assert mel.shape[1] == T
         content = self.content(wav16, T, wav16_float)
         main.wait_stream(side)
@@ -192,7 +249,7 @@ class SVCPipeline:
         return ConvertResult(wav=wav, mel=mel, f0=f0, x0=x0, pcm=e.pcm16(wav) if pcm16 else None)
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                     utt_ids=None, bucketed=False, pcm16=False):
+                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -202,15 +259,19 @@ class SVCPipeline:
         (STFT, Praat frames, convolutions, anti-aliased activations, fade-out) stops at each utterance's own end.
         bucketed=True instead runs one batch per distinct length.
         pcm16=True: each waveform comes back as save_audio's samples instead, int16 [T_i*hop + 2*(fs//20)]
-        (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak)."""
+        (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak).
+        key_shift: semitones, a scalar or one per utterance (shift_f0)."""
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
             raise ValueError("convert_many: wavs24, wavs16, singers (and wavs16_float) must have one entry per utterance")
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
+        shifted = bool(torch.as_tensor(key_shift).any())
         if not bucketed:
             return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float,
                                        fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=ids,
-                                       pcm16=pcm16)
+                                       pcm16=pcm16, **(dict(key_shift=key_shift) if shifted else {}))
+        ks = key_shift.tolist() if hasattr(key_shift, "tolist") else key_shift
+        ks = [float(k) for k in ks] if isinstance(ks, (list, tuple)) else [float(ks)] * n
         buckets = {}
         for i in range(n):
             key = (int(wavs24[i].shape[-1]), int(wavs16[i].shape[-1]),
@@ -226,7 +287,8 @@ class SVCPipeline:
             sing = torch.tensor([int(singers[i]) for i in idx], device=dev, dtype=torch.int32)
             uid = torch.tensor([ids[i] for i in idx], device=dev, dtype=torch.int32)
             res = self.convert(w24, w16, sing, fast_inference=fast_inference, speedup=speedup, seed=seed,
-                               utt_ids=uid, wav16_float=w16f, pcm16=pcm16)
+                               utt_ids=uid, wav16_float=w16f, pcm16=pcm16,
+                               **(dict(key_shift=[ks[i] for i in idx]) if shifted else {}))
             for j, i in enumerate(idx):
                 out[i] = res.pcm[j] if pcm16 else res.wav[j]
         return out
@@ -292,17 +354,18 @@ class SVCPipeline:
         return out
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                       utt_ids=None, pcm16=False):
+                       utt_ids=None, pcm16=False, key_shift=0.0):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
-        [T_b * hop + 2 * (fs // 20)] (svc_pcm16 with the same lengths)."""
+        [T_b * hop + 2 * (fs // 20)] (svc_pcm16 with the same lengths). Each clip's F0 moves onto its own singer's
+        median (shift_f0), then up by key_shift semitones (a scalar or one per clip)."""
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                                        pcm16)
+                                        pcm16, key_shift)
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
-                      float16k=None):
+                      float16k=None, key_shift=0.0):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
@@ -316,10 +379,10 @@ class SVCPipeline:
             wavs24, wavs16 = A.load_batch(sources, self.engine.cfg.fs, self.engine)
             wavs16_float = None
         return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float, fast_inference=fast_inference,
-                                   speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16)
+                                   speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift)
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                        pcm16=False):
+                        pcm16=False, key_shift=0.0):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -333,7 +396,7 @@ class SVCPipeline:
         with torch.cuda.stream(side):
             mel, energy = e.mel_energy(w24, n_samples=n24)
             f0 = self.extract_f0(w24, T, n_samples=n24, T_b=T_b)
-            e.pitch_shift(f0)
+            self.shift_f0(f0, [int(s) for s in singers], key_shift)
         content = self.ragged_content(list(wavs16), T_b, T, wavs16_float)
         main.wait_stream(side)
         for t in (mel, energy, f0):

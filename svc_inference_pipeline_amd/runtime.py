@@ -3,6 +3,7 @@ torch device tensors (PyTorch supplies device memory and the HIP stream; all com
 libsvc_hip.so). Layout of every tensor is time-major [B, T, C] (row = b*T + t).
 """
 import ctypes
+import os
 import threading
 
 import numpy as np
@@ -11,6 +12,7 @@ import torch
 from . import _lib
 from . import weights as W
 from .config import load_stats, noise_schedule
+from .singers import SingerF0Table
 
 MODE_DDPM, MODE_PLMS = 0, 1
 
@@ -34,6 +36,18 @@ def _host_lengths(lengths, B, ctype):
     if len(vals) != B:
         raise ValueError(f"{len(vals)} lengths for a batch of {B}")
     return (ctype * B)(*vals)
+
+
+def _host_f64(v):
+    return v.detach().cpu().numpy().astype(np.float64) if isinstance(v, torch.Tensor) else np.asarray(v, np.float64)
+
+
+def _host_table(values, B, what):
+    """A host f64 table of B entries for the C-ABI from a scalar (repeated) or B values."""
+    a = _host_f64(values).reshape(-1) if np.ndim(_host_f64(values)) else np.full(B, float(values))
+    if a.shape[0] != B:
+        raise ValueError(f"{a.shape[0]} {what} values for a batch of {B}")
+    return (ctypes.c_double * B)(*a.tolist())
 
 
 def mel_frames(n_samples, n_fft=1024, hop=256):
@@ -113,6 +127,9 @@ class SVCEngine:
         # points): SVCPipeline conversions and SVCServer's worker take this lock around a whole conversion
         self.lock = threading.RLock()
         self.device = device
+        # per-singer F0 targets (SVCPipeline.enroll fills it); empty: every singer takes target_f0_median
+        path = getattr(cfg, "singer_f0_file", None)
+        self.singer_f0 = SingerF0Table.load(path) if path and os.path.exists(path) else SingerF0Table()
         self._ctx = ctypes.c_void_p()
         torch.cuda.set_device(device)
         _lib.call("svc_ctx_create", device, ctypes.byref(self._ctx))
@@ -233,13 +250,35 @@ class SVCEngine:
                   float(self.cfg.fs), win, hop, float(lo), float(hi), T, _ptr(f0), _stream())
         return f0
 
-    def pitch_shift(self, f0, target_median=None):
+    def pitch_shift(self, f0, target_median=None, scale=None):
         """In place: f0 *= target_median / median(voiced f0) per utterance
-        (utils/acoustic_feature_extraction.py:33-52). f0 f64 [B, T]."""
+        (utils/acoustic_feature_extraction.py:33-52). f0 f64 [B, T]. target_median: None (the global one of
+        config/stats.json) or a scalar: svc_pitch_shift; a sequence or tensor of B targets, or any `scale` (a scalar or
+        B factors applied after the shift: row b *= (target[b] / med_b) * scale[b]): svc_pitch_shift_ex."""
         B, T = f0.shape
         tm = self.target_f0_median if target_median is None else target_median
-        _lib.call("svc_pitch_shift", self._ctx, _ptr(f0), B, T, float(tm), _stream())
+        per_row = isinstance(tm, (list, tuple, np.ndarray, torch.Tensor)) and np.ndim(_host_f64(tm)) > 0
+        if not per_row and scale is None:
+            _lib.call("svc_pitch_shift", self._ctx, _ptr(f0), B, T, float(tm), _stream())
+            return f0
+        _lib.call("svc_pitch_shift_ex", self._ctx, _ptr(f0), B, T, _host_table(tm, B, "target_median"),
+                  None if scale is None else _host_table(scale, B, "scale"), _stream())
         return f0
+
+    def f0_voiced_median(self, f0, frames=None):
+        """np.median of the voiced (nonzero) cells of f0 f64 [B, T] (or [T]) with t < frames[b] (host ints [B]; None:
+        all T), pooled over the batch (utils/acoustic_feature_extraction.py:21-30) -> (median f64 [1], voiced count
+        int64 [1]) on the device, stream-ordered; the median is NaN where nothing is voiced."""
+        if f0.dim() == 1:
+            f0 = f0[None]
+        if f0.dtype != torch.float64 or f0.dim() != 2:
+            raise ValueError("f0_voiced_median: f0 must be f64 [B, T]")
+        B, T = f0.shape
+        med = torch.empty(1, device=f0.device, dtype=torch.float64)
+        cnt = torch.empty(1, device=f0.device, dtype=torch.int64)
+        _lib.call("svc_f0_voiced_median", self._ctx, _ptr(f0), B, T, _host_lengths(frames, B, ctypes.c_int32),
+                  _ptr(med), _ptr(cnt), _stream())
+        return med, cnt
 
     def whisper_encode(self, wav16):
         """wav16 f32 [B, N16] -> Whisper encoder output f32 [B, n_ctx, D] (utils/whisper.py:13-28)."""

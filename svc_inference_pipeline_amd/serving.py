@@ -53,6 +53,7 @@ class _Request:
     future: Future = field(default_factory=Future)
     file: object = None     # audio.WavInfo of a submit_file request (wav24 / wav16 are decoded by the worker)
     float16k: bool = False  # a file request whose decoding also fills wav16_float (a HuBERT configuration)
+    key_shift: float = 0.0  # semitones on top of the shift to the singer's F0 median
 
 
 class SVCServer:
@@ -82,16 +83,17 @@ class SVCServer:
         self._worker = threading.Thread(target=self._run, name="svc-server", daemon=True)
         self._worker.start()
 
-    def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None) -> Future:
+    def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None, key_shift=0.0) -> Future:
         """Queue one utterance (device tensors: 24 kHz f32 [N], 16 kHz [N16], optional float 16 kHz for
-        ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True)."""
+        ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True).
+        key_shift: semitones for this request, on top of the shift to its singer's F0 median."""
         n = int(wav24.shape[-1])
         if n < 1 or int(wav16.shape[-1]) < 1:
             raise ValueError("SVCServer.submit: empty audio")
         req = _Request(wav24=wav24.reshape(-1), wav16=wav16.reshape(-1), singer=int(singer),
                        utt_id=next(self._ids) if utt_id is None else int(utt_id),
                        wav16_float=None if wav16_float is None else wav16_float.reshape(-1),
-                       frames=self._frames(n), t_submit=time.monotonic())
+                       frames=self._frames(n), t_submit=time.monotonic(), key_shift=float(key_shift))
         if wav24.is_cuda:
             req.stream = torch.cuda.current_stream(wav24.device)
             req.ready = torch.cuda.Event()
@@ -103,7 +105,7 @@ class SVCServer:
             self._cv.notify()
         return req.future
 
-    def submit_file(self, src, singer, utt_id=None) -> Future:
+    def submit_file(self, src, singer, utt_id=None, key_shift=0.0) -> Future:
         """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
         the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
         the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
@@ -112,6 +114,7 @@ class SVCServer:
         16 kHz row (audio.load_contentvec_audio of the file), so for batching it counts as a request with `wav16_float`:
         it shares a batch with tensor requests that carry one, never with tensor requests that do not."""
         req = self._file_request(src, singer, utt_id)
+        req.key_shift = float(key_shift)
         if req.future.done():
             return req.future
         if torch.cuda.is_available():
@@ -139,6 +142,11 @@ class SVCServer:
         req.float16k = self._float16k
         req.frames = self._frames(int(_lib.load().svc_resample_len(info.n_frames, info.sr, int(self._fs))))
         return req
+
+    def enroll(self, singer, sources=None, wavs24=None, max_batch=16):
+        """SVCPipeline.enroll on the server's pipeline (it takes the engine's lock, so it runs between batches): the
+        singer's F0 median from the singer's own recordings becomes the pitch target of later requests."""
+        return self.pipeline.enroll(singer, sources=sources, wavs24=wavs24, max_batch=max_batch)
 
     def close(self, wait=True):
         """Stop accepting requests; the worker finishes every queued request first."""
@@ -235,9 +243,12 @@ class SVCServer:
                         if t is not None and t.is_cuda:
                             t.record_stream(work)
             w16f = [r.wav16_float for r in batch] if batch[0].wav16_float is not None else None
+            kw = dict(self.kw)
+            if any(r.key_shift for r in batch):  # one per request (none shifted: the call as before)
+                kw["key_shift"] = [r.key_shift for r in batch]
             wavs = self.pipeline.convert_ragged([r.wav24 for r in batch], [r.wav16 for r in batch],
                                                 [r.singer for r in batch], wavs16_float=w16f,
-                                                utt_ids=[r.utt_id for r in batch], **self.kw)
+                                                utt_ids=[r.utt_id for r in batch], **kw)
             if torch.cuda.is_available():
                 torch.cuda.current_stream().synchronize()
             self.batches.append([r.utt_id for r in batch])
