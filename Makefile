@@ -29,7 +29,19 @@ build/res_proj.o build/gate_ws.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_D
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -o $@
 
+# Device assembly of every kernel file, with the object rule's flags (per-file additions included). A device-code
+# refactor is proved by `make isa` in the parent tree and in the new one, then tools/isa_diff.py on the two build/isa.
+ISA := $(patsubst $(SRC_DIR)/%.hip,build/isa/%.s,$(SRCS))
+
+isa: $(ISA)
+
+build/isa/%.s: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include/svc_hip.h
+	@mkdir -p build/isa
+	$(HIPCC) $(CXXFLAGS) --cuda-device-only -S -Wno-unused-command-line-argument $< -o $@
+
+build/isa/attention.s: CXXFLAGS += -fno-honor-nans
+
 clean:
 	rm -rf build $(LIB)
 
-.PHONY: all clean
+.PHONY: all clean isa

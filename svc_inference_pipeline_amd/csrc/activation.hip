@@ -8,6 +8,7 @@
 // rounding of the argument u*alpha that the reference itself incurs.
 #include "common.h"
 #include "kernels.h"
+#include "prims.h"
 #include "snake.h"
 
 namespace svc {
@@ -128,9 +129,9 @@ __global__ __launch_bounds__(256) void activation1d_rs_kernel(const TX* __restri
   }
   const SnakeCoef2 kc = snake_coef2(alpha_log, beta_log, c);
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<TX*>(x), (short)0,
-                                                                      (int)((int64_t)B * L * C * sizeof(TX)), 0x00020000);
+                                                                      (int)((int64_t)B * L * C * sizeof(TX)), BUF_CFG);
   const __amdgpu_buffer_rsrc_t ry =
-      __builtin_amdgcn_make_buffer_rsrc(y, (short)0, (int)((int64_t)B * L * ldy * 2), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(y, (short)0, (int)((int64_t)B * L * ldy * 2), BUF_CFG);
   const uint32_t xo = (uint32_t)(((int64_t)b * L * C + c) * sizeof(TX)), yo = (uint32_t)(((int64_t)b * L * ldy + c) * 2);
   const uint32_t xs = (uint32_t)(C * sizeof(TX)), ys = (uint32_t)(ldy * 2);
   if (t0 >= 5 && t0 + R + 5 <= Lb)

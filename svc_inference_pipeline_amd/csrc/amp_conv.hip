@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "prims.h"
 #include "snake.h"
 #include "amp_conv.h"
 
@@ -171,7 +172,7 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
       constexpr int IT = ((CF::BT + 2 * CF::MAXP) * CH + CF::NT - 1) / CF::NT;  // chunks per thread, largest image
       const int r0 = t0 - P, n = rows * CH;
       const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-          const_cast<f16*>(p.x16 + (int64_t)b * L * C), (short)0, Lb * C * 2, 0x00020000);
+          const_cast<f16*>(p.x16 + (int64_t)b * L * C), (short)0, Lb * C * 2, BUF_CFG);
       uint4 v[IT];
       // rows outside [0, Lb) lie outside the descriptor's range (a negative row wraps past it): they load as zeros
 #pragma unroll
@@ -202,7 +203,7 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
     const int nruns = (rows + RUN - 1) / RUN;
     const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void*>(X16 ? (const void*)p.x16 : (const void*)p.x), (short)0,
-        (int)((int64_t)p.B * L * C * sizeof(TX)), 0x00020000);
+        (int)((int64_t)p.B * L * C * sizeof(TX)), BUF_CFG);
     for (int task = tid; task < ngrp * nruns; task += CF::NT) {
       const int cg = task % ngrp, ru = task / ngrp;
       const int c = cg * 2;
@@ -277,9 +278,9 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
     }
     if (e.out32) *reinterpret_cast<float4*>(e.out32 + g) = w;  // may alias add_row / acc32: same element, same thread
     if (e.out16) {
-      union { uint2 u2; f16 h[4]; } pk;
+      H4 pk;
       pk.h[0] = f16_sat(w.x); pk.h[1] = f16_sat(w.y); pk.h[2] = f16_sat(w.z); pk.h[3] = f16_sat(w.w);
-      *reinterpret_cast<uint2*>(e.out16 + g) = pk.u2;
+      *reinterpret_cast<uint2*>(e.out16 + g) = pk.u;
     }
   };
   if (!(p.dbg & 8)) {
@@ -294,10 +295,10 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
     const int blk_bytes = nvalid * C * 4;
     const __amdgpu_buffer_rsrc_t r_ar =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e.add_row ? e.add_row + base : e.bias), (short)0,
-                                          e.add_row ? blk_bytes : 0, 0x00020000);
+                                          e.add_row ? blk_bytes : 0, BUF_CFG);
     const __amdgpu_buffer_rsrc_t r_ac =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(e.acc32 ? e.acc32 + base : e.bias), (short)0,
-                                          e.acc32 ? blk_bytes : 0, 0x00020000);
+                                          e.acc32 ? blk_bytes : 0, BUF_CFG);
     auto epi2 = [&](float4 w, const float4& ar, const float4& ac, int64_t g) __attribute__((always_inline)) {
       if (e.add_row) {
         w.x += ar.x; w.y += ar.y; w.z += ar.z; w.w += ar.w;
@@ -310,9 +311,9 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
       }
       if (e.out32) *reinterpret_cast<float4*>(e.out32 + g) = w;  // may alias add_row / acc32: same element, same thread
       if (e.out16) {
-        union { uint2 u2; f16 h[4]; } pk;
+        H4 pk;
         pk.h[0] = f16_sat(w.x); pk.h[1] = f16_sat(w.y); pk.h[2] = f16_sat(w.z); pk.h[3] = f16_sat(w.w);
-        *reinterpret_cast<uint2*>(e.out16 + g) = pk.u2;
+        *reinterpret_cast<uint2*>(e.out16 + g) = pk.u;
       }
     };
     const bool has_ops = e.add_row || e.acc32;  // (the c1 convs have none: no loads at all)

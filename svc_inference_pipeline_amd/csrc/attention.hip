@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -59,7 +60,6 @@ __device__ __forceinline__ float sum_xor32(float x) {
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
 typedef short short4v __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float float2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 typedef _Float16 half4v __attribute__((ext_vector_type(4)));
@@ -93,9 +93,7 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(const f16* __restrict
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // 1-D grid, remapped so that consecutive logical workgroups (the query blocks of one utterance and head, which read
   // the same K / V) run on one XCD: K / V are fetched into each XCD's L2 once instead of by all eight
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wg = xcd_remap();
   const int nq = (L + ATT_QT - 1) / ATT_QT, H = D / 64;
   const int qblk = wg % nq, h = (wg / nq) % H, b = wg / (nq * H);
   const int ld = 3 * D;
@@ -337,9 +335,9 @@ __global__ __launch_bounds__(256, 3) void attention_kernel(const f16* __restrict
     f16* orow = out + ((int64_t)b * Ls + q) * D + h * 64;
 #pragma unroll
     for (int df = 0; df < 4; ++df) {
-      union { uint2 u; f16 e[4]; } pk;
+      H4 pk;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) pk.e[r] = O::enc_lo(o[df][f][r] * inv);
+      for (int r = 0; r < 4; ++r) pk.h[r] = O::enc_lo(o[df][f][r] * inv);
       *reinterpret_cast<uint2*>(orow + df * 16 + 4 * g) = pk.u;
     }
   }

@@ -18,6 +18,7 @@
 // (2 x 101 fewer launches, but 8 waves per CU leave the epilogue's loads latency-bound), removed.
 #include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -35,30 +36,6 @@ constexpr int DH_LDS = DH_RING_B + 4 * 8192;    // 160 KiB
 __device__ __forceinline__ int dl_sw64(int row, int q) { return q ^ ((row >> 1) & 2); }
 // u image rows of 256 B (128 channels): chunk q at q ^ (row & 15), conflict-free for the GEMM B A fragments
 __device__ __forceinline__ int dl_swg(int row, int q) { return q ^ (row & 15); }
-
-__device__ __forceinline__ void dl_dma(const void* src, unsigned char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void dl_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void dl_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-union DlH4 {
-  uint2 u;
-  f16 h[4];
-};
-
-__device__ __forceinline__ int dl_xcd_remap() {  // consecutive tiles on one XCD
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-}
 
 struct DiffHeadArgs {
   const f16* s16;    // [rows][1152] split-fp16 skip sum
@@ -78,7 +55,7 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
   const int M = p.M;
-  const int m0 = dl_xcd_remap() * DL_BM;
+  const int m0 = xcd_remap() * DL_BM;
   const int fr = lane & 15, fk = lane >> 4;
   const f16* zsrc = zpage + lane * 8;
   constexpr int LDS_ = 3 * DL_C;  // 1152 halves per s16 row / packed weight row
@@ -100,9 +77,9 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
     unsigned char* st = sm + (s & 3) * DH_SLOT_A;
     const bool live = s < DH_S1;
     if (v == 0)
-      dl_dma(live && a_p ? (const void*)(a_p + s * 32) : (const void*)zsrc, st + wave * 1024);
+      lds_dma16(live && a_p ? (const void*)(a_p + s * 32) : (const void*)zsrc, st + wave * 1024);
     else
-      dl_dma(live ? (const void*)(b_p[v - 1] + s * 32) : (const void*)zsrc, st + 8192 + (wave * 3 + v - 1) * 1024);
+      lds_dma16(live ? (const void*)(b_p[v - 1] + s * 32) : (const void*)zsrc, st + 8192 + (wave * 3 + v - 1) * 1024);
   };
   auto issueA = [&](int s_in) {
     int s;
@@ -114,7 +91,7 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
     int s;
     asm volatile("s_mov_b32 %0, %1" : "=s"(s) : "s"(s_in));
     const int ws = s < DL_KS2 ? s : (s < 2 * DL_KS2 ? s + DL_KS2 : s - DL_KS2);
-    dl_dma(s < DH_S1 ? (const void*)(o_p + ws * 32) : (const void*)zsrc, sm + DH_RING_B + (s & 3) * 8192 + wave * 1024);
+    lds_dma16(s < DH_S1 ? (const void*)(o_p + ws * 32) : (const void*)zsrc, sm + DH_RING_B + (s & 3) * 8192 + wave * 1024);
   };
 
   // ---- GEMM A
@@ -165,8 +142,8 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
   };
   auto stepA = [&](int s, half8 (&ca)[4], half8 (&cb)[6], half8 (&na)[4], half8 (&nb6)[6])
                    __attribute__((always_inline)) {
-    dl_vmwait<4>();  // step s + 1 landed (step s + 2 may be in flight)
-    dl_barrier();    // ... for every wave; every wave finished reading step s - 1: its slot (s + 3) & 3 is free
+    vm_wait<4>();  // step s + 1 landed (step s + 2 may be in flight)
+    wg_barrier();  // ... for every wave; every wave finished reading step s - 1: its slot (s + 3) & 3 is free
     int sn;
     asm volatile("s_mov_b32 %0, %1" : "=s"(sn) : "s"(s + 3));
     __builtin_amdgcn_s_setprio(1);
@@ -192,21 +169,21 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
   };
-  dl_vmwait<8>();  // step 0 landed
-  dl_barrier();
+  vm_wait<8>();  // step 0 landed
+  wg_barrier();
   readA(0, af[0], bf[0], -1);
 #pragma unroll 1
   for (int s = 0; s < DH_S1; s += 2) {
     stepA(s, af[0], bf[0], af[1], bf[1]);
     stepA(s + 1, af[1], bf[1], af[0], bf[0]);
   }
-  dl_vmwait<0>();  // the dummy DMAs of the last steps land before the image overlays the ring
+  vm_wait<0>();  // the dummy DMAs of the last steps land before the image overlays the ring
   // u = relu(acc + b_sp); hi = f16(u) goes to the LDS image, lo = f16(u - hi) stays in registers (packed, half the
   // registers of u), so GEMM A's f32 accumulators die here
   const int nb = wn * 96 + fk * 4;
   uint2 ulo[4][6];
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  dl_barrier();  // every wave finished GEMM A's last step: the ring under the image is free
+  lgkm_wait0();
+  wg_barrier();  // every wave finished GEMM A's last step: the ring under the image is free
 #pragma unroll
   for (int j = 0; j < 6; ++j) {
     const int n = nb + j * 16;
@@ -216,7 +193,7 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
       const int row = wm * 64 + i * 16 + fr;
       const float u[4] = {fmaxf(acc[i][j][0] + bi.x, 0.f), fmaxf(acc[i][j][1] + bi.y, 0.f),
                           fmaxf(acc[i][j][2] + bi.z, 0.f), fmaxf(acc[i][j][3] + bi.w, 0.f)};
-      DlH4 hi, lo;
+      H4 hi, lo;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         hi.h[r] = O::enc(u[r]);
@@ -237,8 +214,8 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
 #pragma unroll 1
   for (int s = 0; s < DH_S1; ++s) {
     if (s == 2 * DL_KS2) {  // the lo image replaces the hi image once every wave has finished reading it
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      dl_barrier();
+      lgkm_wait0();
+      wg_barrier();
 #pragma unroll
       for (int j = 0; j < 6; ++j) {
         const int n = nb + j * 16;
@@ -250,9 +227,9 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
         }
       }
     }
-    dl_vmwait<2>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's image writes
-    dl_barrier();
+    vm_wait<2>();
+    lgkm_wait0();  // this wave's image writes
+    wg_barrier();
     int sn;
     asm volatile("s_mov_b32 %0, %1" : "=s"(sn) : "s"(s + 3));
     const int k2 = s % DL_KS2;  // K-step within the 384-channel image
@@ -282,7 +259,7 @@ __global__ __launch_bounds__(DL_NT, 1) void diff_head_kernel(DiffHeadArgs p, con
     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
   }
-  dl_vmwait<0>();  // the dummy DMAs of the last steps land before the workgroup's LDS is released
+  vm_wait<0>();  // the dummy DMAs of the last steps land before the workgroup's LDS is released
   // ---- eps = acc + b_out, columns < n_out
   // both column groups' bias loaded and waited for once, before any store: waited for inside the per-row / per-column
   // branches, the compiler's wait insertion (conservative at their joins) put a vmcnt(0) before every store, each

@@ -8,6 +8,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "median.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -31,8 +32,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       v[i] = xr[i * 64 + lane];
       s += v[i];
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   const float mean = s / (float)D;
   float ss = 0.f;
 #pragma unroll
@@ -41,8 +41,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
       float d = v[i] - mean;
       ss += d * d;
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+  ss = wave_sum(ss);
   const float rstd = 1.0f / sqrtf(ss / (float)D + 1e-5f);
   OutT* yr = y + (int64_t)row * ldy;
 #pragma unroll
@@ -81,6 +80,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
       v[q] = *reinterpret_cast<const float4*>(xr + q * 256 + 4 * lane);
       s += (v[q].x + v[q].y) + (v[q].z + v[q].w);
     }
+  // (the two reductions stay spelled out: through wave_sum this kernel's registers and packed adds come out differently)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   const float mean = s / (float)D;
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
         *reinterpret_cast<float4*>(yr + c) = make_float4(o[0], o[1], o[2], o[3]);
         continue;
       }
-      union { uint2 u; f16 h[4]; } hi, lo;
+      H4 hi, lo;
 #pragma unroll
       for (int k = 0; k < 4; ++k) hi.h[k] = enc16_lo(o[k], bf);
       *reinterpret_cast<uint2*>(yr + c) = hi.u;
@@ -487,7 +487,7 @@ __global__ void plms4_kernel(PlmsArgs p, int rows, int C) {
   if (p.x16) {
     const int64_t r = i4 / C4;
     const int c = (int)(i4 - r * C4) * 4;
-    union { uint2 u; f16 h[4]; } pk;
+    H4 pk;
     const bool bf = p.bf16;
     pk.h[0] = enc16(xn.x, bf); pk.h[1] = enc16(xn.y, bf); pk.h[2] = enc16(xn.z, bf); pk.h[3] = enc16(xn.w, bf);
     *reinterpret_cast<uint2*>(p.x16 + r * p.ld16 + c) = pk.u;
@@ -654,7 +654,7 @@ __device__ double block_select(const double* f, int T, int k, int* red) {
         cnt += ((kk & mask) == prefix) && !(kk & bm);
       }
     }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = wave_sum(cnt);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
     __syncthreads();
@@ -670,26 +670,26 @@ __device__ double block_select(const double* f, int T, int k, int* red) {
   return __longlong_as_double((long long)b);
 }
 
-__global__ __launch_bounds__(256) void pitch_shift_kernel(double* f0, int T, double target) {
-  __shared__ int red[4];
-  double* f = f0 + (int64_t)blockIdx.x * T;
+// np.median of row f's voiced (non-zero) frames, by the 256-thread workgroup (red: 4 ints of LDS)
+__device__ __forceinline__ double voiced_median(const double* f, int T, int* red) {
   int n = 0;
   for (int i = threadIdx.x; i < T; i += blockDim.x) n += f[i] != 0.0;
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
   __syncthreads();
   n = red[0] + red[1] + red[2] + red[3];
   __syncthreads();
-  double med;
-  if (n == 0) {
-    med = __longlong_as_double(0x7FF8000000000000ll);  // np.median of an empty selection is NaN
-  } else if (n & 1) {
-    med = block_select(f, T, n / 2, red);
-  } else {
-    double a = block_select(f, T, n / 2 - 1, red);
-    double b = block_select(f, T, n / 2, red);
-    med = (a + b) / 2.0;
-  }
+  if (n == 0) return __longlong_as_double(0x7FF8000000000000ll);  // np.median of an empty selection is NaN
+  if (n & 1) return block_select(f, T, n / 2, red);
+  const double a = block_select(f, T, n / 2 - 1, red);
+  const double b = block_select(f, T, n / 2, red);
+  return (a + b) / 2.0;
+}
+
+__global__ __launch_bounds__(256) void pitch_shift_kernel(double* f0, int T, double target) {
+  __shared__ int red[4];
+  double* f = f0 + (int64_t)blockIdx.x * T;
+  const double med = voiced_median(f, T, red);
   const double factor = target / med;
   __syncthreads();
   for (int i = threadIdx.x; i < T; i += blockDim.x) f[i] = f[i] * factor;
@@ -707,23 +707,7 @@ __global__ __launch_bounds__(256) void pitch_shift_ex_kernel(double* f0, int T, 
                                                              const double* __restrict__ scale) {
   __shared__ int red[4];
   double* f = f0 + (int64_t)blockIdx.x * T;
-  int n = 0;
-  for (int i = threadIdx.x; i < T; i += blockDim.x) n += f[i] != 0.0;
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = n;
-  __syncthreads();
-  n = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();
-  double med;
-  if (n == 0) {
-    med = __longlong_as_double(0x7FF8000000000000ll);
-  } else if (n & 1) {
-    med = block_select(f, T, n / 2, red);
-  } else {
-    double a = block_select(f, T, n / 2 - 1, red);
-    double b = block_select(f, T, n / 2, red);
-    med = (a + b) / 2.0;
-  }
+  const double med = voiced_median(f, T, red);
   double factor = target[blockIdx.x] / med;
   if (scale) factor = factor * scale[blockIdx.x];
   __syncthreads();

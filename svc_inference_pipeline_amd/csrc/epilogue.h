@@ -7,6 +7,7 @@
 //             the same channel of the filter half.
 #pragma once
 #include "common.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -56,7 +57,7 @@ __device__ __forceinline__ void epilogue_pass(const float* Cs, int m0, int nbase
           if (e.acc32) {
             ac = *reinterpret_cast<const float4*>(e.acc32 + orow * e.ld_acc + n);
           } else {  // split residual: (hi + lo) - the add16 it was stored with
-            union { uint2 u; f16 h[4]; } hi, lo;
+            H4 hi, lo;
             hi.u = *reinterpret_cast<const uint2*>(e.acc16_hi + orow * e.ld_acc + n);
             lo.u = *reinterpret_cast<const uint2*>(e.acc16_lo + orow * e.ld_acc + n);
             const float4 sb = *reinterpret_cast<const float4*>(e.acc_sub + n);
@@ -76,18 +77,18 @@ __device__ __forceinline__ void epilogue_pass(const float* Cs, int m0, int nbase
           const float4 ad = *reinterpret_cast<const float4*>(e.add16 + n);
           w.x += ad.x; w.y += ad.y; w.z += ad.z; w.w += ad.w;
         }
-        union { uint2 u; f16 h[4]; } pk;
+        H4 pk;
         pk.h[0] = O::enc(w.x); pk.h[1] = O::enc(w.y); pk.h[2] = O::enc(w.z); pk.h[3] = O::enc(w.w);
         const int64_t ocol = e.col_block ? (int64_t)(n / e.col_block) * e.col_block_stride + n % e.col_block : n;
         *reinterpret_cast<uint2*>(e.out16 + orow * e.ld16 + ocol) = pk.u;
         if (e.lo16) {
-          union { uint2 u; f16 h[4]; } lo;
+          H4 lo;
           lo.h[0] = O::enc_lo(w.x - O::dec(pk.h[0])); lo.h[1] = O::enc_lo(w.y - O::dec(pk.h[1]));
           lo.h[2] = O::enc_lo(w.z - O::dec(pk.h[2])); lo.h[3] = O::enc_lo(w.w - O::dec(pk.h[3]));
           *reinterpret_cast<uint2*>(e.lo16 + orow * e.ld16 + n) = lo.u;
         }
         if (e.split16) {
-          union { uint2 u; f16 h[4]; } lo;
+          H4 lo;
           lo.h[0] = O::enc_lo(w.x - O::dec(pk.h[0])); lo.h[1] = O::enc_lo(w.y - O::dec(pk.h[1]));
           lo.h[2] = O::enc_lo(w.z - O::dec(pk.h[2])); lo.h[3] = O::enc_lo(w.w - O::dec(pk.h[3]));
           *reinterpret_cast<uint2*>(e.out16 + orow * e.ld16 + e.split16 + n) = lo.u;
@@ -111,7 +112,7 @@ __device__ __forceinline__ void epilogue_pass(const float* Cs, int m0, int nbase
       const float4 b2 = *reinterpret_cast<const float4*>(e.bias + n + 32);
       v1.x += b1.x; v1.y += b1.y; v1.z += b1.z; v1.w += b1.w;
       v2.x += b2.x; v2.y += b2.y; v2.z += b2.z; v2.w += b2.w;
-      union { uint2 u; f16 h[4]; } pk, c1, c2;  // EPI_GATE
+      H4 pk, c1, c2;  // EPI_GATE
       c1.u = *reinterpret_cast<const uint2*>(e.cp + (int64_t)m * e.ld_cp + n);
       c2.u = *reinterpret_cast<const uint2*>(e.cp + (int64_t)m * e.ld_cp + n + 32);
       pk.h[0] = O::enc_lo(gate_act(v1.x + O::dec(c1.h[0]), v2.x + O::dec(c2.h[0])));

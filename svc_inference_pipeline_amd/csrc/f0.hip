@@ -33,6 +33,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "prims.h"
 #include "fft.h"
 
 namespace svc {
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(256) void f0_global_kernel(const float* __restrict_
 }
 
 __device__ double block_sum(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -234,7 +235,7 @@ __device__ double block_sum(double v, double* red) {
 }
 
 __device__ double block_max(double v, double* red) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  v = wave_max(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();

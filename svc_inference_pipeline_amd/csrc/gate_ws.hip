@@ -35,9 +35,7 @@
 
 #include "common.h"
 #include "kernels.h"
-
-// gw_dma clobbers m0 (reserved for the compiler's own LDS-DMA and indexing uses, which all set it right before use)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "prims.h"
 
 namespace svc {
 
@@ -69,8 +67,10 @@ constexpr int GW_LDS_STAMPS = GW_STL + 4 * GW_NSTAMP * 8;  // 153,344 B: the sta
 constexpr int GW_PARTS = 42;          // row parts (x 6 column groups)
 constexpr int GW_GRID = 256;
 constexpr int GW_NT = 512;
-constexpr uint32_t GW_OOR = 0x80000000u;  // a voffset past every descriptor's range (loads return 0, stores drop)
-constexpr uint32_t GW_CFG = 0x00020000u;  // buffer descriptor dword 3 (raw, 32-bit data format)
+// A voffset past every descriptor's range (loads return 0, stores drop). Not prims.h's BUF_OOR (0x7ffffff0): this one is
+// past any extent an int num_records can hold, and it also masks the output stores; both values serve the DMAs here, and
+// it stays this kernel's own so that its code is unchanged.
+constexpr uint32_t GW_OOR = 0x80000000u;
 static_assert(GW_GBYTES % 1024 == 0 && GW_STRIDE % 16 == 0, "ring geometry");
 
 struct GateWsArgs {
@@ -89,33 +89,9 @@ struct GateWsArgs {
   unsigned long long* stamps;  // diagnostics (SVC_GWS_STAMPS, svc_gemm_bench only): s_memtime per workgroup and step
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 gw_desc(const void* base, int64_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, (uint32_t)(bytes > 0 ? bytes : 0), GW_CFG};
-}
-// LDS-DMA of 16 B per lane (lane i's bytes land at lds + 16 i), in inline asm: the compiler neither counts it nor drains
-// it before the LDS reads of other ring slots; the first waves' counted vmcnt waits order it
-__device__ __forceinline__ void gw_dma(u32x4 d, uint32_t voff, unsigned char* lds) {
-  const uint32_t m0 =
-      __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               ::"s"(m0), "v"(voff), "s"(d) : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void gw_vmwait() {
-  static_assert(N >= 0 && N < 64, "vmcnt");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// workgroup barrier behind this wave's LDS writes (the partial accumulators, the prologue's tables)
-__device__ __forceinline__ void gw_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-union GwH4 { uint2 u; f16 h[4]; };
+// The ring is filled by lds_bdma16_raw (prims.h: the compiler neither counts it nor drains it before the LDS reads of
+// other ring slots; the first waves' counted vm_wait order it). The barriers are wg_barrier_lds: behind this wave's LDS
+// writes (the partial accumulators, the prologue's tables).
 
 // Diagnostics (compile-time DBG, svc_gemm_bench / SVC_GWS_DBG / SVC_GWS_STAMPS only): 2 no MFMAs, 4 no gate arithmetic,
 // 8 step stamps. Stamps: s_memtime at step boundaries, [workgroup][kind][GW_NSTAMP] in a buffer nothing else reads.
@@ -284,7 +260,7 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
 
   if (kh == 0) {
     // ------------------------------------------------------------------ first waves: K-steps 0..GW_KA - 1 + ring DMAs
-    const u32x4 dx = gw_desc(a.X, (int64_t)a.M * GW_C * 2);
+    const u32x4 dx = buf_desc(a.X, (int64_t)a.M * GW_C * 2);
     // group g = input rows r_begin - 8 + 32 g .. + 31 into ring slot g % 5; its 25 pieces go to the four first waves
     // round robin (piece p = pair + 4 v): pair 0 issues 7 per group, the others 6. A lane's unit u of piece p -> row
     // u / 50 of the group, 16-B chunk u % 50 (48, 49: the row's padding, read as nothing)
@@ -304,7 +280,7 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
       unsigned char* dst = smw + (g % GW_NG) * GW_GBYTES + pair * 1024;
 #pragma unroll
       for (int v = 0; v < PV; ++v)
-        if (v < PV - 1 || seven) gw_dma(dx, base + pc[v], dst + v * 4096);
+        if (v < PV - 1 || seven) lds_bdma16_raw(dx, base + pc[v], dst + v * 4096);
     };
     issue(0);
     issue(1);
@@ -315,7 +291,7 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
     issue(4);
     GwRow row;
     row.init(a, tvt, r_begin + fr);
-    gw_barrier();  // groups 0 and 1, the zero row and the length table
+    wg_barrier_lds();  // groups 0 and 1, the zero row and the length table
     // Block j reads groups j / 2 .. (j + 1) / 2, so group G's last reader is block 2 G + 1 (the second wave, step
     // 2 G + 2). Group g = (k + 7) / 2 >= 5 is issued at the start of odd steps k >= 3, into the slot of group g - 5,
     // whose last reader finished in step k - 1; its first reader is block 2 g - 1, 5 steps later. At the end of step k,
@@ -333,16 +309,16 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
       row.next(a, tvt);
       gw_stamp_lds<DBG>(smw, 1, k, 0);
       if (k & 1) {
-        if (seven) gw_vmwait<3 * PV>(); else gw_vmwait<3 * (PV - 1)>();
+        if (seven) vm_wait<3 * PV>(); else vm_wait<3 * (PV - 1)>();
       } else {
-        if (seven) gw_vmwait<2 * PV>(); else gw_vmwait<2 * (PV - 1)>();
+        if (seven) vm_wait<2 * PV>(); else vm_wait<2 * (PV - 1)>();
       }
       gw_stamp_lds<DBG>(smw, 2, k, 0);
-      gw_barrier();  // the partial sums of block k; every first wave's pieces of block k + 1's groups
+      wg_barrier_lds();  // the partial sums of block k; every first wave's pieces of block k + 1's groups
     };
     for (int k = 0; k < nsub; ++k) step(k);
-    gw_barrier();  // step nsub: the second waves finish block nsub - 1
-    gw_vmwait<0>();  // (the groups issued past the part land before the workgroup's LDS is released)
+    wg_barrier_lds();  // step nsub: the second waves finish block nsub - 1
+    vm_wait<0>();  // (the groups issued past the part land before the workgroup's LDS is released)
     if (wave == 0) {
       gw_stamp_flush<DBG>(a, smw, 1, nsub);
       gw_stamp_flush<DBG>(a, smw, 2, nsub);
@@ -355,32 +331,32 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
     // A-fragment reads among the MFMAs. These waves are the second-dispatched half: static priority 1 for the whole
     // loop (MI355X_MICROARCH.md, two waves per SIMD, item 4).
     const __amdgpu_buffer_rsrc_t rcp =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.cp), (short)0, a.M * a.ld_cp * 2, GW_CFG);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, (short)0, a.M * a.ldy * 2, GW_CFG);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.cp), (short)0, a.M * a.ld_cp * 2, BUF_CFG);
+    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, (short)0, a.M * a.ldy * 2, BUF_CFG);
     gw_stamp<DBG>(smw, 0);
     load_w(GW_KA, std::integral_constant<int, GW_KB>());
     const float4 bg = *reinterpret_cast<const float4*>(a.bias + ng + 4 * fk);
     const float4 bfv = *reinterpret_cast<const float4*>(a.bias + nf + 4 * fk);
     // conditioner projection of block j, loaded in step j (two steps before its epilogue) into register set j % 3:
     // fixed roles per set (the steady loop is unrolled by 3), so no register move waits on a load
-    auto load_cp = [&](int blk, GwH4* dst) __attribute__((always_inline)) {
+    auto load_cp = [&](int blk, H4* dst) __attribute__((always_inline)) {
       const uint32_t vo = (uint32_t)(r_begin + blk * 16 + fr) * (uint32_t)(a.ld_cp * 2);  // rows past M read 0
       dst[0].u = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rcp, vo + (ng + 4 * fk) * 2, 0, 0));
       dst[1].u = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rcp, vo + (nf + 4 * fk) * 2, 0, 0));
     };
-    GwH4 c0[2], c1[2], c2[2];
+    H4 c0[2], c1[2], c2[2];
     floatx4 pg = {0.f, 0.f, 0.f, 0.f}, pf = {0.f, 0.f, 0.f, 0.f};  // accumulators of the block awaiting its epilogue
     GwRow row;
     row.init(a, tvt, r_begin + fr);
     gw_stamp<DBG>(smw, 1);
-    gw_barrier();  // (pairs with the first waves' prologue barrier)
+    wg_barrier_lds();  // (pairs with the first waves' prologue barrier)
     // (priority 1 on the first waves instead, or on neither: 903.2 / 900.5 / 902.6 and 902.4 / 902.1 / 904.0 against
     // 908.1 / 908.0 / 907.3 audio-s/s, r04s)
     __builtin_amdgcn_s_setprio(1);
     gw_stamp<DBG>(smw, 2);
     // gate of the lane's element i (conv_gemm4's DIRECT epilogue arithmetic, same order), and the block's store (rows
     // past the part are dropped)
-    auto gate_el = [&](int i, const GwH4* cp, const floatx4& ag, const floatx4& af) __attribute__((always_inline)) {
+    auto gate_el = [&](int i, const H4* cp, const floatx4& ag, const floatx4& af) __attribute__((always_inline)) {
       if constexpr ((DBG & 4) != 0) {
         return (f16)(ag[i] + af[(i + 1) & 3]);
       } else {
@@ -389,13 +365,13 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
         return O::enc_lo(gate_act(ag[i] + b_g + O::dec(cp[0].h[i]), af[i] + b_f + O::dec(cp[1].h[i])));
       }
     };
-    auto store_blk = [&](int blk, const GwH4& pk) __attribute__((always_inline)) {
+    auto store_blk = [&](int blk, const H4& pk) __attribute__((always_inline)) {
       const int m = r_begin + blk * 16 + fr;
       const uint32_t vo = m < r_end ? (uint32_t)m * (uint32_t)(a.ldy * 2) + (uint32_t)ch * 2 : GW_OOR;
       buffer_store_b64(pk.u, ry, vo);
     };
-    auto epilogue = [&](int blk, const GwH4* cp, const floatx4& ag, const floatx4& af) __attribute__((always_inline)) {
-      GwH4 pk;
+    auto epilogue = [&](int blk, const H4* cp, const floatx4& ag, const floatx4& af) __attribute__((always_inline)) {
+      H4 pk;
 #pragma unroll
       for (int i = 0; i < 4; ++i) pk.h[i] = gate_el(i, cp, ag, af);
       store_blk(blk, pk);
@@ -412,17 +388,17 @@ __global__ __launch_bounds__(GW_NT, 1) void gate_ws_kernel(GateWsArgs a) {
     };
     auto end_step = [&](int k) __attribute__((always_inline)) {
       gw_stamp_lds<DBG>(smw, 3, k, 256);
-      gw_barrier();
+      wg_barrier_lds();
       gw_stamp<DBG>(smw, 3 + k);
     };
     // steady step k (2 <= k < nsub): cp(k) into LS, MFMAs of block k - 1 with the epilogue of block k - 2 (cp from ES)
     // in their K-step segments: element i at the end of segment (i + 1) GW_KB / 4 - 1 (every element, for any split),
     // the store after the last
-    auto steady = [&](int k, GwH4* ls, const GwH4* es) __attribute__((always_inline)) {
+    auto steady = [&](int k, H4* ls, const H4* es) __attribute__((always_inline)) {
       load_cp(k, ls);
       floatx4 ag, af;
       const floatx4 eg = pg, ef = pf;
-      GwH4 pk;
+      H4 pk;
       auto hook = [&](int s) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)

@@ -3,7 +3,7 @@
 //
 // Same operands and epilogues as conv_gemm2 (A = time-major f16 activations read through per-tap row
 // shifts, B = weights packed [Npad][Kpad], LDS images of 128-B rows with the 16-B chunk XOR swizzle
-// kv ^ (row & 6) applied on the DMA source address), different schedule:
+// sw128, prims.h, applied on the DMA source address), different schedule:
 //
 //   * 8 waves = 2 (M) x 4 (N); wave tile (BM/2) x (BN/4), split into 4 quadrants (m half, n half).
 //     A K-tile (BK = 64) is 4 phases, one quadrant each: phase p reads its quadrant's fragments
@@ -32,6 +32,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "epilogue.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -59,31 +60,6 @@ struct G3 {
   static_assert(QM % 16 == 0 && QN % 16 == 0 && QM % 8 == 0 && QN % 8 == 0 && AH >= 1 && BH >= 1 &&
                     BM % 128 == 0 && BN % 16 == 0, "tile shape");
 };
-
-// 16-B chunk swizzle of the 128-B-row LDS images: conflict-free ds_read_b128 fragment reads (16 consecutive
-// rows per lane group) for every starting row.
-__device__ __forceinline__ int sw3(int row, int kv) { return kv ^ (row & 6); }
-
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void g3_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-__device__ __forceinline__ void g3_dma(const void* src, unsigned char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
-constexpr uint32_t G3_OOR = 0x7ffffff0u;  // a voffset past every descriptor's range: the DMA lands zeros
-__device__ __forceinline__ void g3_bdma(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, unsigned char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, (int)voff, (int)soff,
-                                           0, 0);
-}
 
 // row (within the A or B image) of element i of half-tile h, for a half made of blocks of Q rows
 // every W rows: rows w*W + h*Q + [0, Q)
@@ -113,9 +89,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
   const int grp = wave >> 2;  // stagger group: one wave of each per SIMD
   const bool bfull = CF::BH == CF::BHL || wave < CF::BW;  // this wave issues BH (else BHL) B pieces per half-tile
 
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+  const int wgid = xcd_remap();
   const int tile_n = wgid % a.ntiles_n, tile_m = wgid / a.ntiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int M = a.B * a.T_out;
@@ -123,7 +97,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
   const f16* zsrc = zpage + lane * 8;
 
   // ---- DMA slots. A half h, instruction v: image rows rb .. rb+7, lane -> row rb + (lane >> 3),
-  // LDS chunk lane & 7 holding logical k-chunk kv = sw3(row, lane & 7).
+  // LDS chunk lane & 7 holding logical k-chunk kv = sw128(row, lane & 7).
   int a_rb[2][CF::AH], a_kv[2][CF::AH], a_t[2][CF::AH], a_tin[2][CF::AH];
   const f16* a_p[2][CF::AH];
   uint32_t a_row[2][CF::AH], a_voff[2][CF::AH];  // CP64: byte offset of the lane's A row at tap shift 0 / this tap
@@ -134,7 +108,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
       const int u = wave + 8 * v;
       const int rb = half_row(8 * u, h, CF::QM, CF::WTM);
       const int row = rb + (lane >> 3);
-      const int kv = sw3(row, lane & 7);
+      const int kv = sw128(row, lane & 7);
       a_rb[h][v] = rb;
       a_kv[h][v] = kv;
       const int m = m0 + row;
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
         a_p[h][v] = a.X;
         a_row[h][v] = 0u;
       }
-      a_voff[h][v] = G3_OOR;
+      a_voff[h][v] = BUF_OOR;
     }
   int b_rb[2][CF::BH];
   const f16* b_p[2][CF::BH];
@@ -163,14 +137,14 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
       const int rb = half_row(8 * u, h, CF::QN, CF::WTN);
       const int row = rb + (lane >> 3);
       b_rb[h][v] = rb;
-      b_p[h][v] = a.W + (int64_t)(n0 + row) * a.Kpad + sw3(row, lane & 7) * 8;
-      b_voff[h][v] = (uint32_t)(((n0 + row) * a.Kpad + sw3(row, lane & 7) * 8) * 2);
+      b_p[h][v] = a.W + (int64_t)(n0 + row) * a.Kpad + sw128(row, lane & 7) * 8;
+      b_voff[h][v] = (uint32_t)(((n0 + row) * a.Kpad + sw128(row, lane & 7) * 8) * 2);
     }
   // CP64 descriptors (unused otherwise); extents checked on the host (< 1 GiB: no voffset + soffset wraps)
   const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.X), (short)0, a.B * a.T_in * a.ldx * 2, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.X), (short)0, a.B * a.T_in * a.ldx * 2, BUF_CFG);
   const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.W), (short)0, a.ntiles_n * BN * a.Kpad * 2, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.W), (short)0, a.ntiles_n * BN * a.Kpad * 2, BUF_CFG);
 
   auto a_img = [&](int kt) { return sm3 + (kt & 1) * CF::TILE; };
   auto b_img = [&](int kt) { return sm3 + (kt & 1) * CF::TILE + BM * 128; };
@@ -188,14 +162,14 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
 #pragma unroll
           for (int v = 0; v < CF::AH; ++v) {
             const int st = a_t[h][v] + shift;
-            a_voff[h][v] = st >= 0 && st < a_tin[h][v] ? a_row[h][v] + (uint32_t)(shift * a.ldx * 2) : G3_OOR;
+            a_voff[h][v] = st >= 0 && st < a_tin[h][v] ? a_row[h][v] + (uint32_t)(shift * a.ldx * 2) : BUF_OOR;
           }
         }
 #pragma unroll
-        for (int v = 0; v < CF::AH; ++v) g3_bdma(rx, a_voff[h][v], (uint32_t)(c0 * 2), dst + a_rb[h][v] * 128);
+        for (int v = 0; v < CF::AH; ++v) lds_bdma16(rx, a_voff[h][v], (uint32_t)(c0 * 2), dst + a_rb[h][v] * 128);
       } else {
 #pragma unroll
-        for (int v = 0; v < CF::AH; ++v) g3_bdma(rx, G3_OOR, 0u, dst + a_rb[h][v] * 128);
+        for (int v = 0; v < CF::AH; ++v) lds_bdma16(rx, BUF_OOR, 0u, dst + a_rb[h][v] * 128);
       }
     } else {
 #pragma unroll
@@ -209,7 +183,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
         const bool ok = kt < nk && kg < a.K && st >= 0 && st < a_tin[h][v];
         // a_p already carries the lane's kv * 8 column offset: add the tap-local column base only
         const f16* src = ok ? a_p[h][v] + (int64_t)st * a.ldx + (c - a_kv[h][v] * 8) : zsrc;
-        g3_dma(src, dst + a_rb[h][v] * 128);
+        lds_dma16(src, dst + a_rb[h][v] * 128);
       }
     }
   };
@@ -219,13 +193,13 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
 #pragma unroll
       for (int v = 0; v < CF::BH; ++v)
         if (v < CF::BHL || bfull)
-          g3_bdma(rw, kt < nk ? b_voff[h][v] : G3_OOR, (uint32_t)(kt * 128), dst + b_rb[h][v] * 128);
+          lds_bdma16(rw, kt < nk ? b_voff[h][v] : BUF_OOR, (uint32_t)(kt * 128), dst + b_rb[h][v] * 128);
     } else {
       const int koff = kt * 64;
 #pragma unroll
       for (int v = 0; v < CF::BH; ++v)
         if (v < CF::BHL || bfull)
-          g3_dma(kt < nk ? (const void*)(b_p[h][v] + koff) : (const void*)zsrc, dst + b_rb[h][v] * 128);
+          lds_dma16(kt < nk ? (const void*)(b_p[h][v] + koff) : (const void*)zsrc, dst + b_rb[h][v] * 128);
     }
   };
 
@@ -260,7 +234,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
         const int row = wm * CF::WTM + QMI * CF::QM + i * 16 + fr;
 #pragma unroll
         for (int s = 0; s < 2; ++s)
-          af[i][s] = *reinterpret_cast<const half8*>(Ab + row * 128 + (sw3(row, s * 4 + fk) << 4));
+          af[i][s] = *reinterpret_cast<const half8*>(Ab + row * 128 + (sw128(row, s * 4 + fk) << 4));
       }
     }
     if constexpr (QMI == 0) {
@@ -269,7 +243,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
         const int row = wn * CF::WTN + QNI * CF::QN + j * 16 + fr;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          const half8 v = *reinterpret_cast<const half8*>(Bb + row * 128 + (sw3(row, s * 4 + fk) << 4));
+          const half8 v = *reinterpret_cast<const half8*>(Bb + row * 128 + (sw128(row, s * 4 + fk) << 4));
           if constexpr (QNI == 0)
             bfl[j][s] = v;
           else
@@ -290,7 +264,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
       issue_b(0, kt + 2);
       g3_wait();
     }
-    g3_barrier();
+    wg_barrier();
     // ---- M section
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -306,7 +280,7 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
             acc[QMI][QNI][i][j] = O::mfma(af[i][s], b, acc[QMI][QNI][i][j]);
         }
     __builtin_amdgcn_s_setprio(0);
-    g3_barrier();
+    wg_barrier();
   };
 
   // ---- prologue: A-lo(0), B-lo(0), B-hi(0), A-hi(0), A-lo(1), B-lo(1) in flight; retire the first two (the state
@@ -318,8 +292,8 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
   issue_a(0, 1);
   issue_b(0, 1);
   g3_wait();
-  g3_barrier();
-  if (grp == 1) g3_barrier();  // stagger: group 1 runs one barrier behind group 0
+  wg_barrier();
+  if (grp == 1) wg_barrier();  // stagger: group 1 runs one barrier behind group 0
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
   for (int kt = 0; kt < nk; ++kt) {
@@ -328,10 +302,9 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
     phase(I1{}, I0{}, kt);
     phase(I1{}, I1{}, kt);
   }
-  if (grp == 0) g3_barrier();
+  if (grp == 0) wg_barrier();
   vm_wait<0>();  // trailing dummy DMAs land before the ring is reused for C staging (or the workgroup ends)
   if constexpr (FORM != G3_LDS) {
-    union H4 { uint2 u; f16 h[4]; };
     // column groups (y, j): packed columns nq .. nq + 3; their bias (and per-column vectors) loaded once
     float4 cb[2][CF::FQN], cs[2][CF::FQN], ca[2][CF::FQN];
 #pragma unroll
@@ -359,9 +332,9 @@ __global__ __launch_bounds__(512, 1) void conv_gemm3_kernel(ConvGemmArgs a, EpiA
     const void* opa = FORM == G3_SPLIT ? (const void*)e.acc16_hi : (const void*)e.add_row;
     const void* opb = FORM == G3_SPLIT ? (const void*)e.acc16_lo : (const void*)e.acc32;
     const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(opa ? opa : (const void*)e.bias), (short)0, opa ? 0x7fffffff : 0, 0x00020000);
+        const_cast<void*>(opa ? opa : (const void*)e.bias), (short)0, opa ? 0x7fffffff : 0, BUF_CFG);
     const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void*>(opb ? opb : (const void*)e.bias), (short)0, opb ? 0x7fffffff : 0, 0x00020000);
+        const_cast<void*>(opb ? opb : (const void*)e.bias), (short)0, opb ? 0x7fffffff : 0, BUF_CFG);
 #pragma unroll
     for (int x = 0; x < 2; ++x)
 #pragma unroll

@@ -9,13 +9,14 @@
 //     one barrier per K-tile;
 //     with the C-staging epilogue the workgroup needs 66 KiB, so two workgroups share a CU and one's prologue /
 //     epilogue runs beside the other's MFMAs (inter-workgroup overlap in place of intra-workgroup staggering);
-//   * the same operand images (128-B rows, 16-B chunk swizzle kv ^ (row & 6)), A loader (per-tap row shifts, zero
+//   * the same operand images (128-B rows, 16-B chunk swizzle sw128), A loader (per-tap row shifts, zero
 //     rows outside the utterance) and LDS-staged vector epilogue (epilogue.h) as conv_gemm3.
 #include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
 #include "epilogue.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -24,33 +25,10 @@ constexpr int G4_STAGE = (G4_BM + G4_BN) * 128;  // 32 KiB
 constexpr int G4_LDC = G4_BN + 4;
 constexpr int G4_LDS = (2 * G4_STAGE > G4_BM * G4_LDC * 4) ? 2 * G4_STAGE : G4_BM * G4_LDC * 4;
 
-__device__ __forceinline__ int sw4(int row, int kv) { return kv ^ (row & 6); }
-
-__device__ __forceinline__ void g4_dma(const void* src, unsigned char* lds) {
-  __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds, 16, 0, 0);
-}
-
 // CP64 form: LDS-DMA through buffer descriptors. A lane's 32-bit voffset is fixed per conv tap (per K-tile for W) and
 // the K-tile's channel offset is the scalar soffset, so the K-loop issues its DMAs with no per-lane address arithmetic;
 // a padding row (outside its utterance) gets a voffset past the descriptor's range, which the hardware bounds check
-// turns into zeros.
-constexpr uint32_t G4_OOR = 0x7ffffff0u;
-__device__ __forceinline__ void g4_bdma(__amdgpu_buffer_rsrc_t r, uint32_t voff, uint32_t soff, unsigned char* lds) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, (int)voff, (int)soff,
-                                           0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void g4_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ void g4_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
+// turns into zeros (lds_bdma16 and BUF_OOR, prims.h).
 // DIRECT (gate epilogue only): the MFMAs run with the operands swapped, so a lane's accumulator holds 4 CONSECUTIVE
 // packed columns of one output row, and the gate column block j (< 2) and its filter partner j + 2 (packed column + 32)
 // sit in the same lane. The gate is then applied in registers: no 64 KiB f32 round trip through LDS, the conditioner
@@ -58,13 +36,7 @@ __device__ __forceinline__ void g4_barrier() {
 // (8 B) per row.
 // (Round 2 also had a register read-modify-write epilogue for the DiffSVC output projection here; faster alone, slower
 // beside the sampler's other stream, it was removed in round 3.)
-// blockIdx -> a workgroup index whose consecutive values land on one XCD (tiles sharing A rows share that XCD's L2)
-__device__ __forceinline__ int g4_xcd_remap() {
-  const int nwg = gridDim.x, orig = blockIdx.x;
-  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-}
-
+//
 // One 128 x 128 output tile (index wgid, N-tiles fastest) of the implicit GEMM, by the calling 256-thread workgroup.
 template <bool CP64, bool PAIR, bool DIRECT, bool BF>
 __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const EpiArgs& e, const f16* zpage,
@@ -88,7 +60,7 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
 #pragma unroll
   for (int v = 0; v < 4; ++v) {
     const int row = (wave * 4 + v) * 8 + (lane >> 3);
-    const int kv = sw4(row, lane & 7);
+    const int kv = sw128(row, lane & 7);
     a_kv[v] = kv;
     const int m = m0 + row;
     if (m < M) {
@@ -103,15 +75,15 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
       a_p[v] = a.X;
       a_row[v] = 0u;
     }
-    a_voff[v] = G4_OOR;
+    a_voff[v] = BUF_OOR;
     b_p[v] = a.W + (int64_t)(n0 + row) * a.Kpad + kv * 8;
     b_voff[v] = (uint32_t)(((n0 + row) * a.Kpad + kv * 8) * 2);
   }
   // CP64 descriptors (unused otherwise); extents checked on the host (< 1 GiB: no voffset + soffset wraps)
   const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.X), (short)0, a.B * a.T_in * a.ldx * 2, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.X), (short)0, a.B * a.T_in * a.ldx * 2, BUF_CFG);
   const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.W), (short)0, a.ntiles_n * G4_BN * a.Kpad * 2, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.W), (short)0, a.ntiles_n * G4_BN * a.Kpad * 2, BUF_CFG);
   auto issue = [&](int kt) {
     unsigned char* A = sm4 + (kt & 1) * G4_STAGE;
     unsigned char* Bm = A + G4_BM * 128;
@@ -124,13 +96,13 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const int st = a_t[v] + shift;
-          a_voff[v] = st >= 0 && st < a_tin[v] ? a_row[v] + (uint32_t)(shift * a.ldx * 2) : G4_OOR;
+          a_voff[v] = st >= 0 && st < a_tin[v] ? a_row[v] + (uint32_t)(shift * a.ldx * 2) : BUF_OOR;
         }
       }
 #pragma unroll
-      for (int v = 0; v < 4; ++v) g4_bdma(rx, a_voff[v], (uint32_t)(c0 * 2), A + (wave * 4 + v) * 1024);
+      for (int v = 0; v < 4; ++v) lds_bdma16(rx, a_voff[v], (uint32_t)(c0 * 2), A + (wave * 4 + v) * 1024);
 #pragma unroll
-      for (int v = 0; v < 4; ++v) g4_bdma(rw, b_voff[v], (uint32_t)(kt * 128), Bm + (wave * 4 + v) * 1024);
+      for (int v = 0; v < 4; ++v) lds_bdma16(rw, b_voff[v], (uint32_t)(kt * 128), Bm + (wave * 4 + v) * 1024);
       return;
     } else {
       const bool live = kt < nk;
@@ -143,12 +115,12 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
         const int c = kg - tap * a.Cp;
         const int st = a_t[v] + tap * a.tap_mul + a.tap_add;
         const bool ok = live && kg < a.K && st >= 0 && st < a_tin[v];
-        g4_dma(ok ? (const void*)(a_p[v] + (int64_t)st * a.ldx + (c - a_kv[v] * 8)) : (const void*)zsrc,
-               A + (wave * 4 + v) * 1024);
+        lds_dma16(ok ? (const void*)(a_p[v] + (int64_t)st * a.ldx + (c - a_kv[v] * 8)) : (const void*)zsrc,
+                  A + (wave * 4 + v) * 1024);
       }
 #pragma unroll
       for (int v = 0; v < 4; ++v)
-        g4_dma(live ? (const void*)(b_p[v] + kt * 64) : (const void*)zsrc, Bm + (wave * 4 + v) * 1024);
+        lds_dma16(live ? (const void*)(b_p[v] + kt * 64) : (const void*)zsrc, Bm + (wave * 4 + v) * 1024);
     }
   };
 
@@ -162,7 +134,6 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
   // DIRECT epilogue operands: rows m0 + wm*64 + i*16 + fr, packed columns nw + j*16 + fk*4 .. +3 (j < 2) and + 32
   const int nw = n0 + wn * 64;
   const bool wave_cols = nw < a.N;
-  union H4 { uint2 u; f16 h[4]; };
   H4 cpg[4][2], cpf[4][2];
   float4 bg[2], bfl[2];
 #pragma unroll
@@ -194,8 +165,8 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
   // has finished reading that stage in iteration kt - 1) and lands under the MFMAs of iteration kt.
   issue(0);
   for (int kt = 0; kt < nk; ++kt) {
-    g4_vmwait<0>();  // this wave's DMAs of stage kt have landed (nothing younger is outstanding)
-    g4_barrier();    // ... and everyone's; stage (kt + 1) & 1 is free
+    vm_wait<0>();  // this wave's DMAs of stage kt have landed (nothing younger is outstanding)
+    wg_barrier();    // ... and everyone's; stage (kt + 1) & 1 is free
     if (kt + 1 < nk) issue(kt + 1);
     if constexpr (DIRECT) {
       if (kt + 1 == nk) {  // under the last K-tile's MFMAs (spreading these over earlier K-steps measured no better)
@@ -213,12 +184,12 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int row = wm * 64 + i * 16 + fr;
-        af[i] = *reinterpret_cast<const half8*>(A + row * 128 + (sw4(row, s * 4 + fk) << 4));
+        af[i] = *reinterpret_cast<const half8*>(A + row * 128 + (sw128(row, s * 4 + fk) << 4));
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int row = wn * 64 + j * 16 + fr;
-        bf[j] = *reinterpret_cast<const half8*>(Bm + row * 128 + (sw4(row, s * 4 + fk) << 4));
+        bf[j] = *reinterpret_cast<const half8*>(Bm + row * 128 + (sw128(row, s * 4 + fk) << 4));
       }
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -270,7 +241,7 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
     }
     return;
   }
-  g4_vmwait<0>();
+  vm_wait<0>();
   __syncthreads();
   // acc[i][j][r] = C[wm*64 + i*16 + fk*4 + r][wn*64 + j*16 + fr]
   float* Cs = reinterpret_cast<float*>(sm4);
@@ -287,7 +258,7 @@ __device__ __forceinline__ void conv_gemm4_tile(const ConvGemmArgs& a, const Epi
 template <bool CP64, bool PAIR, bool DIRECT, bool BF>
 __global__ __launch_bounds__(256, 2) void conv_gemm4_kernel(ConvGemmArgs a, EpiArgs e, const f16* zpage, float inv_cp) {
   extern __shared__ __align__(16) unsigned char sm4[];
-  conv_gemm4_tile<CP64, PAIR, DIRECT, BF>(a, e, zpage, inv_cp, g4_xcd_remap(), sm4);
+  conv_gemm4_tile<CP64, PAIR, DIRECT, BF>(a, e, zpage, inv_cp, xcd_remap(), sm4);
 }
 
 // direct: the register gate epilogue (paired epilogues only), otherwise the LDS-staged epilogue_pass

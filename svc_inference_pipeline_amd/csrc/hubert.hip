@@ -14,6 +14,7 @@
 //   layernorm_dual: LayerNorm writing both the f32 residual stream and its f16 GEMM operand (post-LN layers).
 #include "common.h"
 #include "kernels.h"
+#include "prims.h"
 
 namespace svc {
 
@@ -201,8 +202,7 @@ __global__ __launch_bounds__(256) void layernorm_dual_kernel(const float* x, con
       v[i] = xr[i * 64 + lane];
       s += v[i];
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  s = wave_sum(s);
   const float mean = s / (float)D;
   float ss = 0.f;
 #pragma unroll
@@ -211,8 +211,7 @@ __global__ __launch_bounds__(256) void layernorm_dual_kernel(const float* x, con
       const float d = v[i] - mean;
       ss += d * d;
     }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+  ss = wave_sum(ss);
   const float rstd = 1.0f / sqrtf(ss / (float)D + 1e-5f);
 #pragma unroll
   for (int i = 0; i < 16; ++i)

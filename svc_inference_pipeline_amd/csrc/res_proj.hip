@@ -24,9 +24,7 @@
 // result is bit-identical to the tiled GEMM with its LDS-staged split epilogue (tests/test_gpu_ops.py).
 #include "common.h"
 #include "kernels.h"
-
-// rp_dma clobbers m0 (reserved for the compiler's own LDS-DMA and indexing uses, which all set it right before use)
-#pragma clang diagnostic ignored "-Winline-asm"
+#include "prims.h"
 
 namespace svc {
 
@@ -39,7 +37,6 @@ constexpr int RP_GB = RP_ROWS * RP_C * 2;  // g image of a tile: 12 KiB = 12 DMA
 constexpr int RP_HB = RP_ROWS * RP_H * 2;  // hi (or lo) image of a tile's half: 6 KiB = 6
 constexpr int RP_SLOT = RP_GB + 2 * RP_HB;  // 24 KiB: 24 DMA wave-instructions, 2 per wave
 constexpr int RP_ND = 2, RP_NS = 2;       // per wave and tile: DMA wave-instructions, stores
-constexpr uint32_t RP_CFG = 0x00020000u;  // buffer descriptor dword 3 (raw, 32-bit data format)
 
 struct ResProjArgs {
   const f16* g;       // [M][384] gate outputs of the layer
@@ -61,32 +58,9 @@ struct ResProjArgs {
 __device__ __forceinline__ int rp_gchunk(int r, int q) { return r * 48 + (q ^ r); }
 __device__ __forceinline__ int rp_hchunk(int r, int q) { return r * 24 + (q ^ ((r >> 1) & 7)); }
 
-// LDS-DMA of 16 B per lane (lane i's bytes land at lds + 16 i) through a buffer descriptor, in inline asm: the compiler
-// does not see it, so it neither drains it before every LDS read it cannot prove disjoint (it did, for the hi / lo
-// reads of the ring) nor counts it; the loop's own vmcnt waits (rp_wait_tile) order the ring
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ u32x4 rp_desc(const f16* base, int64_t bytes) {
-  const uint64_t a = (uint64_t)(uintptr_t)base;
-  return u32x4{(uint32_t)a, (uint32_t)(a >> 32) & 0xffffu, (uint32_t)(bytes > 0 ? bytes : 0), RP_CFG};
-}
-__device__ __forceinline__ void rp_dma(u32x4 d, uint32_t voff, unsigned char* lds) {
-  const uint32_t m0 =
-      __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds);
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               ::"s"(m0), "v"(voff), "s"(d) : "memory", "m0");
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rp_rsrc(const f16* base, int64_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(base), (short)0, (int)(bytes > 0 ? bytes : 0), RP_CFG);
-}
-
-// wait until at most N of this wave's vector-memory operations are outstanding (loads, LDS-DMAs and stores count
-// together, in issue order)
-template <int N>
-__device__ __forceinline__ void rp_vmwait() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
+// The tiles come in by lds_bdma16_raw (prims.h): the compiler drained its own LDS-DMA before every hi / lo read of the
+// ring that it could not prove disjoint; the loop's own vmcnt waits (rp_wait_tile) order the ring instead.
+//
 // Every wave issues RP_ND DMA wave-instructions and RP_NS buffer stores per iteration, whatever the rows (tiles past
 // the end DMA zeros, stores past M are dropped by the range check), so the number of its vector-memory operations
 // younger than its DMAs of tile t is a compile-time count:
@@ -94,7 +68,7 @@ __device__ __forceinline__ void rp_vmwait() {
 template <int D, int T>
 __device__ __forceinline__ void rp_wait_case() {
   constexpr int n = T < D - 1 ? (D - 2 - T) * RP_ND + T * (RP_ND + RP_NS) : RP_NS + (D - 2) * (RP_ND + RP_NS);
-  rp_vmwait<n>();
+  vm_wait<n>();
 }
 template <int D>
 __device__ __forceinline__ void rp_wait_tile(int t) {
@@ -107,9 +81,6 @@ __device__ __forceinline__ void rp_wait_tile(int t) {
 }
 
 // RP_D: ring slots (tiles); DMAs run RP_D - 1 tiles ahead
-constexpr float RP_SQRT2 = SQRT2_F;
-__device__ __forceinline__ float rp_div_sqrt2(float x) { return div_sqrt2_exact(x); }
-
 // 101-104 VGPRs as built (keep it at or under 104): three waves per SIMD (312 registers) then fit beside one gate GEMM
 // workgroup (184), which is what
 // lets the other sampler stream's gate GEMM and this stream share a CU (r03o / r03p)
@@ -169,10 +140,10 @@ __global__ __launch_bounds__(RP_NT, 1) void res_proj_kernel(ResProjArgs p) {
     unsigned char* slot = smr + (t % RP_D) * RP_SLOT;
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
-      rp_dma(rp_desc(src[v] + off, bytes - hoff[v]), voff[v], slot + dst[v]);
+      lds_bdma16_raw(buf_desc(src[v] + off, bytes - hoff[v]), voff[v], slot + dst[v]);
     }
   };
-  const __amdgpu_buffer_rsrc_t sh = rp_rsrc(p.hi, (int64_t)p.M * RP_C * 2), sl = rp_rsrc(p.lo, (int64_t)p.M * RP_C * 2);
+  const __amdgpu_buffer_rsrc_t sh = buf_rsrc(p.hi, (int64_t)p.M * RP_C * 2), sl = buf_rsrc(p.lo, (int64_t)p.M * RP_C * 2);
 
 #pragma unroll
   for (int t = 0; t < RP_D - 1; ++t) issue(t);
@@ -187,7 +158,7 @@ __global__ __launch_bounds__(RP_NT, 1) void res_proj_kernel(ResProjArgs p) {
 
     // this lane's hi / lo: row fr, columns n0 + 4 fk .. + 3 = chunk 2 wave + (fk >> 1) of the half, 8-B half fk & 1
     const int hb = rp_hchunk(fr, 2 * wave + (fk >> 1)) * 16 + (fk & 1) * 8;
-    union { uint2 u; f16 h[4]; } hi, lo, ph, pl;
+    H4 hi, lo, ph, pl;
     hi.u = *reinterpret_cast<const uint2*>(slot + RP_GB + hb);
     lo.u = *reinterpret_cast<const uint2*>(slot + RP_GB + RP_HB + hb);
     floatx4 acc = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -199,7 +170,7 @@ __global__ __launch_bounds__(RP_NT, 1) void res_proj_kernel(ResProjArgs p) {
     const float s4[4] = {sb.x, sb.y, sb.z, sb.w}, a4[4] = {ad.x, ad.y, ad.z, ad.w};
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float x = rp_div_sqrt2(((O::dec(hi.h[r]) + O::dec(lo.h[r])) - s4[r]) + v[r]);
+      const float x = div_sqrt2_exact(((O::dec(hi.h[r]) + O::dec(lo.h[r])) - s4[r]) + v[r]);
       const float wv = x + a4[r];
       ph.h[r] = O::enc(wv);
       pl.h[r] = O::enc_lo(wv - O::dec(ph.h[r]));
@@ -210,7 +181,7 @@ __global__ __launch_bounds__(RP_NT, 1) void res_proj_kernel(ResProjArgs p) {
     buffer_store_b64(pl.u, sl, vo);
     __builtin_amdgcn_sched_barrier(0);
   }
-  rp_vmwait<0>();  // (the remaining DMAs of tiles past the end land before the workgroup's LDS is released)
+  vm_wait<0>();  // (the remaining DMAs of tiles past the end land before the workgroup's LDS is released)
 }
 
 // W_res (packed [>= 384][ldw], W[n][k]) -> fragment order Wf[half][wave][kc][lane][8]: 16 B per thread
@@ -237,7 +208,7 @@ size_t res_proj_pack_elems() { return (size_t)RP_C * RP_C; }
 int res_proj(const f16* g, const f16* Wf, const float* bias, const float* sub, const float* add, float div, f16* hi,
              f16* lo, int M, bool bf16, int lanes_cap, hipStream_t s) {
   SVC_REQUIRE(M >= 0 && Wf, "res_proj: M %d, packed weights %p", M, (const void*)Wf);
-  SVC_REQUIRE(div == RP_SQRT2, "res_proj: the residual divisor is sqrt(2) (modules/diffsvc.py:232)");
+  SVC_REQUIRE(div == SQRT2_F, "res_proj: the residual divisor is sqrt(2) (modules/diffsvc.py:232)");
   if (M == 0) return SVC_OK;
   SVC_REQUIRE((int64_t)M * RP_C * 2 < (1ll << 31) - (1 << 20), "res_proj: %d rows exceed the 32-bit buffer range", M);
   SVC_REQUIRE(((uintptr_t)g & 15) == 0 && ((uintptr_t)Wf & 15) == 0 && ((uintptr_t)hi & 15) == 0 &&
@@ -336,21 +307,21 @@ __global__ __launch_bounds__(MP_NT, 1) void mel_proj_kernel(MelProjArgs p) {
     auto issue = [&](int t) {  // tile t of this workgroup into slot t % MP_D (tiles past the end read zeros)
       const int row0 = (blockIdx.x + t * G) * 16;
       const bool live = row0 < p.M;
-      const u32x4 d = rp_desc(p.x + (live ? (int64_t)row0 * p.ldx : 0), live ? (int64_t)(p.M - row0) * rowb : 0);
+      const u32x4 d = buf_desc(p.x + (live ? (int64_t)row0 * p.ldx : 0), live ? (int64_t)(p.M - row0) * rowb : 0);
       unsigned char* slot = smm + (t % MP_D) * MP_SLOT;
 #pragma unroll
-      for (int v = 0; v < 4; ++v) rp_dma(d, src[v], slot + v * 1024);
+      for (int v = 0; v < 4; ++v) lds_bdma16_raw(d, src[v], slot + v * 1024);
     };
 #pragma unroll
     for (int t = 0; t < MP_D - 1; ++t) issue(t);
     for (int t = 0; t < p.iters; ++t) {
-      rp_vmwait<(MP_D - 2) * 4>();  // tile t landed (tiles t + 1 .. t + MP_D - 2 may be in flight)
+      vm_wait<(MP_D - 2) * 4>();  // tile t landed (tiles t + 1 .. t + MP_D - 2 may be in flight)
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();  // every compute wave finished tile t - 1: slot (t - 1) % MP_D is free
       __builtin_amdgcn_sched_barrier(0);
       issue(t + MP_D - 1);
     }
-    rp_vmwait<0>();  // (the DMAs of tiles past the end land before the workgroup's LDS is released)
+    vm_wait<0>();  // (the DMAs of tiles past the end land before the workgroup's LDS is released)
     return;
   }
   // ---- compute waves
@@ -368,7 +339,7 @@ __global__ __launch_bounds__(MP_NT, 1) void mel_proj_kernel(MelProjArgs p) {
     bi[j] = *reinterpret_cast<const float4*>(p.bias + n);
     ad[j] = *reinterpret_cast<const float4*>(p.add + n);
   }
-  const __amdgpu_buffer_rsrc_t sh = rp_rsrc(p.hi, (int64_t)p.M * RP_C * 2), sl = rp_rsrc(p.lo, (int64_t)p.M * RP_C * 2);
+  const __amdgpu_buffer_rsrc_t sh = buf_rsrc(p.hi, (int64_t)p.M * RP_C * 2), sl = buf_rsrc(p.lo, (int64_t)p.M * RP_C * 2);
   const half8 zero = {};
   for (int t = 0; t < p.iters; ++t) {
     __builtin_amdgcn_sched_barrier(0);
@@ -385,7 +356,7 @@ __global__ __launch_bounds__(MP_NT, 1) void mel_proj_kernel(MelProjArgs p) {
       for (int j = 0; j < 2; ++j) acc[j] = O::mfma(w[j][kc], a, acc[j]);  // acc[r] = C[row fr][n + r]
     }
     const uint32_t rowo = (uint32_t)((blockIdx.x + t * G) * 16 + fr) * (RP_C * 2);
-    union { uint2 u; f16 h[4]; } ph[2], pl[2];
+    H4 ph[2], pl[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const float b4[4] = {bi[j].x, bi[j].y, bi[j].z, bi[j].w}, a4[4] = {ad[j].x, ad[j].y, ad[j].z, ad[j].w};
