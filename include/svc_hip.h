@@ -17,6 +17,8 @@
  *   svc_map_content_ragged <- utils/hubert.py:83-134 get_mapped_features / utils/whisper.py:31-81, per utterance
  *   svc_condition       <- modules/encoder.py:165-201 EncoderFramework.forward
  *   svc_diffsvc_sample  <- modules/diffsvcrepo_inference.py:154-240 svc_model_inference (DDPM or PLMS)
+ *   svc_diffsvc_sample_from <- the same from noise level k_step - 1 (Diff-SVC's shallow diffusion)
+ *   svc_mel_normalize   <- utils/acoustic_feature_extraction.py:75-80 normalize_mel_channel
  *   svc_bigvgan         <- utils/acoustic_feature_extraction.py:83-97 denormalize_mel_channel
  *                          + modules/bigvgan_inference.py:29-44 synthesis_audios (Generator + trim + fade)
  *   svc_load_pcm        <- utils/audio.py:10-55 load_audio_torch + utils/whisper_extractor/audio.py:22-49 load_audio
@@ -252,6 +254,28 @@ svc_status svc_diffsvc_sample(svc_ctx* ctx, const float* cond, int B, int T, con
 svc_status svc_diffsvc_eps(svc_ctx* ctx, const float* cond, const float* x, int B, int T, const int32_t* frames, int t,
                            float* eps, void* stream);
 
+/* normalize_mel_channel (utils/acoustic_feature_extraction.py:75-80) with the context's statistics, the inverse of the
+   de-normaliser in svc_bigvgan: mel f32 [B*T][n_mel] as svc_mel_energy writes it -> x_norm f32 [B*T][n_mel],
+   (mel - mel_min) / (mel_max - mel_min + 1e-12) * 2 - 1 per channel in f32, not clamped. frames: see Ragged batches;
+   rows past an utterance's end are zeros. Needs stats.mel_min / stats.mel_max (a context without a mapper may carry
+   them alone: svc_mel_normalize + svc_bigvgan is copy-synthesis through the vocoder). */
+svc_status svc_mel_normalize(svc_ctx* ctx, const float* mel, int B, int T, const int32_t* frames, float* x_norm,
+                             void* stream);
+
+/* Shallow diffusion (Diff-SVC's k_step): svc_diffsvc_sample started at noise level k_step - 1 (1 <= k_step <= steps)
+   instead of from pure noise. The start state is exactly one of
+     mel_src  f32 [B*T][n_mel], the source clip's un-normalised mel (svc_mel_energy's): normalised as svc_mel_normalize
+              does and noised forward, x = sqrt(ac[k-1]) y + sqrt(1 - ac[k-1]) z, z ~ N(0, 1) drawn on the device as
+              svc_op_init_noise draws with counter word 1 = 0xFFFFFFFE (utt_ids required);
+     x_start  f32 [B*T][n_mel], an already noised state.
+   DDPM runs steps k_step - 1 .. 0 (noise, if given, is [k_step][B*T][n_mel], first row for step k_step - 1); PLMS runs
+   i = ((k_step - 1) / interval) * interval, ... , 0 with an empty history at its first iteration. k_step = steps with
+   x_start = x_T is svc_diffsvc_sample bit for bit. SVC_ERR_INVALID: k_step out of range, both or neither of mel_src /
+   x_start, a NULL utt_ids when something is drawn on the device (mel_src; DDPM without noise). */
+svc_status svc_diffsvc_sample_from(svc_ctx* ctx, const float* cond, int B, int T, const int32_t* frames, int mode,
+                                   int interval, int k_step, const float* mel_src, const float* x_start,
+                                   const float* noise, uint64_t seed, const int32_t* utt_ids, float* x0, void* stream);
+
 /* A13+A14+A15: x0 f32 [B*T][n_mel] (normalised) -> wav [B][T*256] f32 (denorm, Generator, tanh, fade-out).
    frames (host int32 [B] or NULL): ragged batch, utterance b's waveform is frames[b]*256 samples (fade-out at its end,
    zeros after).
@@ -393,6 +417,14 @@ svc_status svc_op_layernorm(const float* x, const float* g, const float* b, int 
  * utt_ids[b], 0x5356434B} and key {seed low word, seed high word}, Box-Muller on its first two words. x16 is required. */
 svc_status svc_op_init_noise(uint64_t seed, const int32_t* utt_ids, int B, int T, int C, float std, float* x, void* x16,
                              int ld16, int bf16, void* stream);
+/* svc_diffsvc_sample_from's start state from mel_src, one launch: y = (mel - mel_min) / (mel_max - mel_min + 1e-12) * 2
+ * - 1 per channel (mel_min, mel_max f32 [C]), x [B*T][C] = sqrt_ac y + sqrt_1mac z. z [B*T][C] given, or NULL: drawn as
+ * in svc_op_init_noise with counter word 1 = 0xFFFFFFFE, which needs utt_ids (both NULL is SVC_ERR_INVALID). frames
+ * (DEVICE int32 [B] or NULL): rows t >= frames[b] get 0 in x and x16. x16 is optional. Four channels per thread when
+ * C % 4 == 0, ld16 % 4 == 0, the f32 pointers are 16-byte and x16 8-byte aligned, else one. */
+svc_status svc_op_q_sample(const float* mel, const float* mel_min, const float* mel_max, int B, int T, int C,
+                           float sqrt_ac, float sqrt_1mac, const float* z, uint64_t seed, const int32_t* utt_ids,
+                           const int32_t* frames, float* x, void* x16, int ld16, int bf16, void* stream);
 /* One PLMS update on [rows][C]: e' = (c0 e0 + c1 e1 + ...) / div over the first ne (1..4) histories (the others may
  * be NULL), xout = xin + d (A xin - Bc e'); xout may be xin. Optional outputs: x16 and e_avg_out (e'). Four channels
  * per thread when C % 4 == 0, ld16 % 4 == 0, the f32 pointers are 16-byte and x16 8-byte aligned, else one. */

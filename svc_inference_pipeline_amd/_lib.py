@@ -46,6 +46,9 @@ PROTOTYPES = {
     "svc_condition_indices": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "svc_diffsvc_sample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                    c_uint64, c_void_p, c_void_p, c_void_p]),
+    "svc_diffsvc_sample_from": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "svc_mel_normalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "svc_diffsvc_eps": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "svc_bigvgan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "svc_load_pcm": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64,
@@ -78,6 +81,8 @@ PROTOTYPES = {
     "svc_op_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "svc_op_init_noise": (c_int, [c_uint64, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int,
                                   c_void_p]),
+    "svc_op_q_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_uint64,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "svc_op_plms_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                    c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_int, c_void_p]),

@@ -350,6 +350,21 @@ struct DdpmArgs {
   const float* z; uint64_t seed; const int* utt_ids; int step;
   int bf16;  // x16 holds bfloat16 operands
 };
+// Shallow diffusion's start state (stage_diffsvc.hip svc_diffsvc_sample_from, elementwise.hip q_sample): the source
+// mel normalised per channel, y = (mel - mn) / (mx - mn + 1e-12) * 2 - 1 (utils/acoustic_feature_extraction.py:75-80,
+// no clamp), and noised forward, x = a y + b z with z given or drawn. noised = 0: x = y (svc_mel_normalize).
+struct QSampleArgs {
+  const float* mel;      // [B*T][C] un-normalised
+  const float *mn, *mx;  // [C] the per-channel statistics
+  int noised;
+  float a, b;            // sqrt(alphas_cumprod[K - 1]), sqrt(1 - alphas_cumprod[K - 1])
+  const float* z;        // [B*T][C] given, or NULL: drawn with step word 0xFFFFFFFE (needs utt_ids)
+  uint64_t seed; const int* utt_ids;
+  const int* tv;         // ragged batch (device, optional): rows t >= tv[b] get 0 in both copies
+  float* x;              // [B*T][C]
+  f16* x16; int ld16;    // optional 16-bit operand copy, columns 0..C-1 of rows of ld16 halves
+  int bf16;
+};
 // Kernel-selection switches: the measured production choices by default, other values select the earlier or
 // alternative kernel forms that the parity tests cover and the A/B benches compare (DESIGN.md records each result).
 // A context copies the defaults at creation, where an SVC_<NAME> environment variable overrides each (so a whole

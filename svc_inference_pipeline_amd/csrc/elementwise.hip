@@ -1,6 +1,6 @@
 // Bandwidth-bound kernels of the SVC path on gfx950: LayerNorm (fp32 statistics), content mapping,
 // conditioner bucketize,
-// sampler updates (DDPM / PLMS), mel de-normalisation, conv_post+tanh+fade.
+// sampler updates (DDPM / PLMS), mel normalisation + q_sample, mel de-normalisation, conv_post+tanh+fade.
 // All tensors are time-major [rows = b*T + t][channels].
 #include <cstdlib>
 #include <type_traits>
@@ -557,6 +557,101 @@ int init_noise(float* x, f16* x16, int ld16, int B, int T, int C, uint64_t seed,
   int64_t n = (int64_t)rows * C;
   hipLaunchKernelGGL(init_noise_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, x, x16, ld16, T, C, seed, utt_ids, rows,
                      std, bf);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
+// Shallow diffusion's start state (QSampleArgs, common.h): normalize_mel_channel
+// (utils/acoustic_feature_extraction.py:75-80, no clamp) and Diff-SVC's q_sample in one pass; the normalised mel stays in
+// registers. One element, the same operations in both kernel forms: the quotient and the product by 2 cannot contract,
+// and the one multiply-add is spelled as an fma.
+__device__ __forceinline__ float q_sample_math(float mel, float mn, float mx, float a, float bz, bool noised) {
+  const float y = (mel - mn) / (mx - mn + 1e-12f) * 2.0f - 1.0f;
+  return noised ? fmaf(a, y, bz) : y;
+}
+
+// z of element (t, c) of utterance b: given, or the Philox draw with a step word of its own (0xFFFFFFFE: the x_T draw
+// has 0xFFFFFFFF, DDPM step i has i), keyed by (t, c) like them
+__device__ __forceinline__ float q_sample_z(const QSampleArgs& q, int64_t i, int b, int t, int C, int c) {
+  return q.z ? q.z[i] : philox_normal(q.seed, (uint32_t)q.utt_ids[b], 0xFFFFFFFEu, (uint32_t)(t * C + c));
+}
+
+template <bool NOISED>
+__global__ void q_sample_kernel(QSampleArgs q, int T, int C, int rows) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)rows * C) return;
+  const int64_t r = i / C;
+  const int c = (int)(i - r * C);
+  const int b = (int)(r / T), t = (int)(r - (int64_t)b * T);
+  float v = 0.f;  // rows past the utterance's end: +0 in both copies
+  if (!q.tv || t < q.tv[b]) {
+    const float bz = NOISED ? q.b * q_sample_z(q, i, b, t, C, c) : 0.f;
+    v = q_sample_math(q.mel[i], q.mn[c], q.mx[c], q.a, bz, NOISED);
+  }
+  q.x[i] = v;
+  if (q.x16) q.x16[r * q.ld16 + c] = enc16(v, q.bf16);
+}
+
+// 4 consecutive channels per thread (C % 4 == 0, 16-B aligned f32 rows and statistics, 8-B aligned x16 rows): 16-B
+// loads and stores, an 8-B 16-bit store, a quarter of the threads; per element the operations of q_sample_kernel
+template <bool NOISED>
+__global__ void q_sample4_kernel(QSampleArgs q, int T, int C, int rows) {
+  const int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int C4 = C >> 2;
+  if (i4 >= (int64_t)rows * C4) return;
+  const int64_t r = i4 / C4, i = i4 * 4;
+  const int c = (int)(i4 - r * C4) * 4;
+  const int b = (int)(r / T), t = (int)(r - (int64_t)b * T);
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  if (!q.tv || t < q.tv[b]) {
+    const float4 m = *reinterpret_cast<const float4*>(q.mel + i);
+    const float4 mn = *reinterpret_cast<const float4*>(q.mn + c);
+    const float4 mx = *reinterpret_cast<const float4*>(q.mx + c);
+    float bz[4] = {0.f, 0.f, 0.f, 0.f};
+    if (NOISED) {
+      if (q.z) {
+        const float4 z = *reinterpret_cast<const float4*>(q.z + i);
+        bz[0] = q.b * z.x; bz[1] = q.b * z.y; bz[2] = q.b * z.z; bz[3] = q.b * z.w;
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) bz[k] = q.b * q_sample_z(q, i + k, b, t, C, c + k);
+      }
+    }
+    v[0] = q_sample_math(m.x, mn.x, mx.x, q.a, bz[0], NOISED);
+    v[1] = q_sample_math(m.y, mn.y, mx.y, q.a, bz[1], NOISED);
+    v[2] = q_sample_math(m.z, mn.z, mx.z, q.a, bz[2], NOISED);
+    v[3] = q_sample_math(m.w, mn.w, mx.w, q.a, bz[3], NOISED);
+  }
+  *reinterpret_cast<float4*>(q.x + i) = make_float4(v[0], v[1], v[2], v[3]);
+  if (q.x16) {
+    H4 pk;
+    const bool bf = q.bf16;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pk.h[k] = enc16(v[k], bf);
+    *reinterpret_cast<uint2*>(q.x16 + r * q.ld16 + c) = pk.u;
+  }
+}
+
+// the 4-channel form's layout conditions (q_sample4_kernel)
+static bool q_sample_vec4_ok(const QSampleArgs& q, int C) {
+  bool vec = C % 4 == 0 && (!q.x16 || q.ld16 % 4 == 0) && ((uintptr_t)q.x16 & 7) == 0;
+  const void* ptrs[] = {q.mel, q.mn, q.mx, q.noised ? q.z : nullptr, q.x};
+  for (const void* p : ptrs) vec = vec && ((uintptr_t)p & 15) == 0;
+  return vec;
+}
+
+int q_sample(const QSampleArgs& q, int B, int T, int C, hipStream_t s) {
+  const int rows = B * T;
+  const int64_t n = (int64_t)rows * C;
+  const bool vec = q_sample_vec4_ok(q, C);
+  const dim3 grid((unsigned)cdiv64(vec ? n / 4 : n, 256));
+  if (q.noised) {
+    if (vec) hipLaunchKernelGGL(q_sample4_kernel<true>, grid, dim3(256), 0, s, q, T, C, rows);
+    else hipLaunchKernelGGL(q_sample_kernel<true>, grid, dim3(256), 0, s, q, T, C, rows);
+  } else {
+    if (vec) hipLaunchKernelGGL(q_sample4_kernel<false>, grid, dim3(256), 0, s, q, T, C, rows);
+    else hipLaunchKernelGGL(q_sample_kernel<false>, grid, dim3(256), 0, s, q, T, C, rows);
+  }
   SVC_LAUNCH_CHECK();
   return SVC_OK;
 }

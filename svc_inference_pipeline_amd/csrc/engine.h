@@ -238,6 +238,7 @@ int build_features(svc_ctx* c);
 int build_whisper(svc_ctx* c);
 int build_hubert(svc_ctx* c);
 int build_mapper(svc_ctx* c);
+int build_stats(svc_ctx* c);
 int build_vocoder(svc_ctx* c);
 // stage_diffsvc.hip
 int stage_frames(StageRing& ring, const int32_t* frames, int B, int T, hipStream_t s, const int** dev_out);

@@ -383,6 +383,7 @@ svc_status svc_ctx_finalize(svc_ctx* c) {
   if (any_w && (st = build_whisper(c))) return st;
   if (any_h && (st = build_hubert(c))) return st;
   if (any_m && (st = build_mapper(c))) return st;
+  if (!any_m && c->params.count("stats.mel_min") && (st = build_stats(c))) return st;  // vocoder-only copy-synthesis
   c->pack_bf16 = false;  // BigVGAN stays binary16
   if (any_v && (st = build_vocoder(c))) return st;
   c->params.clear();  // host arrays are no longer referenced

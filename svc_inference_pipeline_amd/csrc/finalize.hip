@@ -784,10 +784,19 @@ int build_mapper(svc_ctx* c) {
     const double pv = betas[i] * (1.0 - prev) / (1.0 - ac);
     c->plogvar[i] = (float)log(pv > 1e-20 ? pv : 1e-20);
   }
+  if ((st = build_stats(c))) return st;
+  c->has_mapper = true;
+  return SVC_OK;
+}
+
+// the per-channel mel statistics: the de-normaliser in front of the vocoder and the normaliser (svc_mel_normalize,
+// shallow diffusion) read them. A context without a mapper may carry them alone (copy-synthesis through the vocoder).
+int build_stats(svc_ctx* c) {
+  const int nmel = c->n_mel = (int)cfgv(c, "mapper.n_mel", 100);
   GETP(mn, "stats.mel_min", nmel);
   GETP(mx, "stats.mel_max", nmel);
+  int st;
   if ((st = upload_param(c, mn, &c->mel_min)) || (st = upload_param(c, mx, &c->mel_max))) return st;
-  c->has_mapper = true;
   return SVC_OK;
 }
 

@@ -27,6 +27,7 @@ int plms_update(const PlmsArgs& p, int rows, int C, hipStream_t s);
 int ddpm_update(float* x, const float* eps, f16* x16, int ld16, int B, int T, int C, const DdpmArgs& a, hipStream_t s);
 int init_noise(float* x, f16* x16, int ld16, int B, int T, int C, uint64_t seed, const int* utt_ids, float std,
                hipStream_t s, bool bf);
+int q_sample(const QSampleArgs& q, int B, int T, int C, hipStream_t s);
 int conv_post(const f16* a, int lda, int B, int L, int C, const float* w, float bias, const float* fade, int nfade,
               float* out, hipStream_t s, const int* tv = nullptr, int tv_mul = 1);
 int zero_tail_rows(float* x, int B, int T, int C, const int* Tb, hipStream_t s);

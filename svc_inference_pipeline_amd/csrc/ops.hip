@@ -276,6 +276,31 @@ svc_status svc_op_init_noise(uint64_t seed, const int32_t* utt_ids, int B, int T
   return init_noise(x, (f16*)x16, ld16, B, T, C, seed, utt_ids, std, (hipStream_t)stream, bf16 != 0);
 }
 
+svc_status svc_op_q_sample(const float* mel, const float* mel_min, const float* mel_max, int B, int T, int C,
+                           float sqrt_ac, float sqrt_1mac, const float* z, uint64_t seed, const int32_t* utt_ids,
+                           const int32_t* frames, float* x, void* x16, int ld16, int bf16, void* stream) {
+  SVC_REQUIRE(mel && mel_min && mel_max && x && B > 0 && T > 0 && C > 0 && (!x16 || ld16 >= C),
+              "op_q_sample: bad args");
+  SVC_REQUIRE((int64_t)B * T * C <= INT32_MAX, "op_q_sample: B*T*C past 2^31");
+  SVC_REQUIRE(z || utt_ids, "op_q_sample: device noise (z NULL) needs utt_ids");
+  QSampleArgs q{};
+  q.mel = mel;
+  q.mn = mel_min;
+  q.mx = mel_max;
+  q.noised = 1;
+  q.a = sqrt_ac;
+  q.b = sqrt_1mac;
+  q.z = z;
+  q.seed = seed;
+  q.utt_ids = utt_ids;
+  q.tv = frames;
+  q.x = x;
+  q.x16 = (f16*)x16;
+  q.ld16 = ld16;
+  q.bf16 = bf16 != 0;
+  return q_sample(q, B, T, C, (hipStream_t)stream);
+}
+
 svc_status svc_op_plms_update(const float* e0, const float* e1, const float* e2, const float* e3, float c0, float c1,
                               float c2, float c3, int ne, float div, float d, float A, float Bc, const float* xin,
                               float* xout, void* x16, int ld16, float* e_avg_out, int bf16, int rows, int C,

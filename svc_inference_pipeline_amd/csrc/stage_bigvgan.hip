@@ -7,7 +7,7 @@ extern "C" {
 svc_status svc_bigvgan(svc_ctx* c, const float* x0, int B, int T, const int32_t* frames, float* wav, float* mel_out,
                        void* stream) {
   CTX_READY(c);
-  SVC_REQUIRE(c->has_vocoder && c->has_mapper, "vocoder (and mapper stats) not loaded");
+  SVC_REQUIRE(c->has_vocoder && c->mel_min && c->mel_max, "vocoder (and mapper stats) not loaded");
   hipStream_t s = (hipStream_t)stream;
   // ragged batches: utterance b has frames[b] mel frames; at a point where the signal is `mul` times the mel rate
   // its valid length is tv[b] * mul, and every conv / activation / the fade-out ends there

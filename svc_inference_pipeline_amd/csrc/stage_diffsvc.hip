@@ -167,10 +167,14 @@ int stage_frames(StageRing& ring, const int32_t* frames, int B, int T, hipStream
 
 }  // namespace svc
 
-static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* tv, int mode, int interval,
-                       const float* x_T, const float* noise, uint64_t seed, const int32_t* utt_ids, float* x0,
-                       hipStream_t stream) {
+// K (1..steps): the sampler starts at noise level K - 1, DDPM at step K - 1 and PLMS at ((K - 1) / interval) * interval
+// with an empty history; K = steps is the whole schedule (svc_diffsvc_sample). The start state is x_T when given, else
+// mel_src normalised and noised forward to level K - 1 (q_sample), else the x_T draw. noise (DDPM): [K][B*T][n_mel].
+static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* tv, int mode, int interval, int K,
+                       const float* x_T, const float* mel_src, const float* noise, uint64_t seed,
+                       const int32_t* utt_ids, float* x0, hipStream_t stream) {
   SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
+  SVC_REQUIRE(K >= 1 && K <= c->steps, "sample: k_step %d outside [1, %d]", K, c->steps);
   SVC_REQUIRE(mode == SVC_MODE_DDPM || (mode == SVC_MODE_PLMS && interval >= 1), "sample: mode %d interval %d", mode,
               interval);
   SVC_REQUIRE(x_T || utt_ids, "sample: need x_T or utt_ids for device noise");
@@ -195,6 +199,23 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
   if (x_T) {
     SVC_HIP_CHECK(hipMemcpyAsync(x, x_T, (size_t)rows * nm * 4, hipMemcpyDeviceToDevice, s));
     if ((st = f32_to_f16(x, nm, x16, ld16, rows, nm, ld16, s, c->bf16))) return st;
+  } else if (mel_src) {
+    const float ac = c->alphas_cumprod_f32[K - 1];
+    QSampleArgs q{};
+    q.mel = mel_src;
+    q.mn = c->mel_min;
+    q.mx = c->mel_max;
+    q.noised = 1;
+    q.a = sqrtf(ac);
+    q.b = sqrtf(1.0f - ac);
+    q.seed = seed;
+    q.utt_ids = utt_ids;
+    q.tv = tv;
+    q.x = x;
+    q.x16 = x16;
+    q.ld16 = ld16;
+    q.bf16 = c->bf16;
+    if ((st = q_sample(q, B, T, nm, s))) return st;
   } else {
     if ((st = init_noise(x, x16, ld16, B, T, nm, seed, utt_ids, 1.0f / 1.2f, s, c->bf16))) return st;
   }
@@ -225,7 +246,7 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
   };
 
   if (mode == SVC_MODE_DDPM) {
-    for (int i = c->steps - 1; i >= 0; --i) {
+    for (int i = K - 1; i >= 0; --i) {
       for (int h = 0; h < S; ++h) {
         const Sub& u = sub[h];
         const size_t r = u.r0;
@@ -238,7 +259,7 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
         a.c1 = c->pc1[i];
         a.c2 = c->pc2[i];
         a.sigma = i > 0 ? expf(0.5f * c->plogvar[i]) : 0.0f;
-        a.z = noise ? noise + (size_t)(c->steps - 1 - i) * rows * nm + r * nm : nullptr;
+        a.z = noise ? noise + (size_t)(K - 1 - i) * rows * nm + r * nm : nullptr;
         a.seed = seed;
         a.utt_ids = utt_ids ? utt_ids + u.b0 : nullptr;
         a.step = i;
@@ -251,7 +272,7 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
   // PLMS: history ring of 4 epsilons + the first step's predictor buffers (the ring position is shared)
   int nh = 0, head = 0;  // hist slots: newest at hist[(head - 1) mod 5]
   const std::vector<float>& ac = c->alphas_cumprod_f32;
-  for (int i = ((c->steps - 1) / interval) * interval; i >= 0; i -= interval) {
+  for (int i = ((K - 1) / interval) * interval; i >= 0; i -= interval) {
     const int tp = i - interval > 0 ? i - interval : 0;
     // get_x_pred coefficients in f32 exactly as the reference's tensor ops (:96-113)
     const float a_t = ac[i], a_prev = ac[tp];
@@ -365,9 +386,47 @@ svc_status svc_diffsvc_sample(svc_ctx* c, const float* cond, int B, int T, const
   const int* tv;
   RingRetire retire_(c->lens_main, s);
   int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
-  if (st || (st = sample_impl(c, cond, B, T, tv, mode, interval, x_T, noise, seed, utt_ids, x0, s))) return st;
+  if (st ||
+      (st = sample_impl(c, cond, B, T, tv, mode, interval, c->steps, x_T, nullptr, noise, seed, utt_ids, x0, s)))
+    return st;
   // frames past an utterance's end hold no sample: zero them
   return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+}
+
+svc_status svc_diffsvc_sample_from(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames, int mode,
+                                   int interval, int k_step, const float* mel_src, const float* x_start,
+                                   const float* noise, uint64_t seed, const int32_t* utt_ids, float* x0,
+                                   void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE((mel_src != nullptr) != (x_start != nullptr), "sample_from: give exactly one of mel_src and x_start");
+  SVC_REQUIRE(!mel_src || utt_ids, "sample_from: mel_src draws the forward noise on the device and needs utt_ids");
+  hipStream_t s = (hipStream_t)stream;
+  const int* tv;
+  RingRetire retire_(c->lens_main, s);
+  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
+  if (st ||
+      (st = sample_impl(c, cond, B, T, tv, mode, interval, k_step, x_start, mel_src, noise, seed, utt_ids, x0, s)))
+    return st;
+  return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+}
+
+// normalize_mel_channel (utils/acoustic_feature_extraction.py:75-80) with the context's statistics
+svc_status svc_mel_normalize(svc_ctx* c, const float* mel, int B, int T, const int32_t* frames, float* x_norm,
+                             void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(c->mel_min && c->mel_max, "mel_normalize: mel statistics (stats.mel_min / stats.mel_max) not loaded");
+  SVC_REQUIRE(mel && x_norm && B > 0 && T > 0 && (int64_t)B * T * c->n_mel <= INT32_MAX, "mel_normalize: bad args");
+  hipStream_t s = (hipStream_t)stream;
+  const int* tv;
+  RingRetire retire_(c->lens_main, s);
+  if (int st = stage_frames(c->lens_main, frames, B, T, s, &tv)) return st;
+  QSampleArgs q{};
+  q.mel = mel;
+  q.mn = c->mel_min;
+  q.mx = c->mel_max;
+  q.tv = tv;
+  q.x = x_norm;
+  return q_sample(q, B, T, c->n_mel, s);
 }
 
 }  // extern "C"

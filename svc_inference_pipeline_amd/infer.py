@@ -7,6 +7,8 @@ converted wav, on one MI355X through libsvc_hip.so.
     python -m svc_inference_pipeline_amd.infer --singer-f0 f0.json --singer svcc_CDF1 --enroll r1.wav r2.wav ...
         # measure the singer's voiced F0 median from the singer's own recordings and keep it in f0.json
     python -m svc_inference_pipeline_amd.infer --singer-f0 f0.json --key 2 --wav a.wav ...   # use it; 2 semitones up
+    python -m svc_inference_pipeline_amd.infer --k-step 300 --fast --wav a.wav ...   # shallow diffusion from step 300
+    python -m svc_inference_pipeline_amd.infer --resynth --vocoder-ckpt vocoder.pt --wav a.wav   # vocoder only
 
 Same sequence as the reference: acoustic features (mel, energy, Praat F0) -> pitch shift to the target
 singer -> Whisper (and / or ContentVec, --hubert-ckpt) content features -> DiffSVC sampler (DDPM-1000 by default, PLMS with --fast, as
@@ -27,7 +29,7 @@ from . import audio as A
 from . import config as C
 from . import weights as W
 from .pipeline import SVCPipeline, hubert_content_type, wants_float16k
-from .runtime import SVCEngine
+from .runtime import SVCEngine, check_k_step, mel_frames
 from .singers import SingerF0Table
 
 
@@ -69,10 +71,34 @@ def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckp
                      vocoder_state=st["vocoder"], **kw)
 
 
+def build_vocoder_engine(cfg, device=0, vocoder_ckpt=None, random_weights=None, seed=0):
+    """--resynth's engine: the vocoder and the mel statistics, no mapper and no content encoder."""
+    if random_weights:
+        return SVCEngine(cfg, device, vocoder_state=W.make_vocoder_state(cfg.vocoder, seed))
+    if not vocoder_ckpt:
+        raise SystemExit("--resynth needs --vocoder-ckpt (or --random-weights)")
+    return SVCEngine(cfg, device, vocoder_state=W.load_checkpoints(vocoder_path=vocoder_ckpt)["vocoder"])
+
+
+def resynth_files(engine, cfg, wav_paths):
+    """--resynth: every file's own mel through the vocoder alone (SVCPipeline.resynthesize, one ragged batch) ->
+    list of (save_audio's int16 samples, T_i)."""
+    w24 = A.load_batch(list(wav_paths), cfg.fs, engine)[0]
+    w24 = [w.reshape(-1) for w in w24]
+    pad, n24 = SVCPipeline._pad_stack(w24)
+    wav = SVCPipeline(engine).resynthesize(pad, n_samples=n24)
+    hop = cfg.hop_length
+    T_b = [mel_frames(k, cfg.n_fft, hop) for k in n24]
+    pcm = engine.pcm16(wav, n_samples=[t * hop for t in T_b])
+    sil2 = pcm.shape[1] - wav.shape[1]
+    return [(pcm[i, :t * hop + sil2].cpu().numpy(), t) for i, t in enumerate(T_b)]
+
+
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                 f0_method="parselmouth", pcm16=False, key_shift=0.0):
+                 f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None):
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
-    the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16)."""
+    the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16). k_step: shallow diffusion
+    (SVCPipeline.convert)."""
     # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
     wav16f = None
     if wants_float16k(cfg):  # and utils/hubert.py:137-143's float 16 kHz copy from the same stage
@@ -87,12 +113,13 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
     res = SVCPipeline(engine, f0_method=f0_method).convert(wav24[None].contiguous(), wav16[None].contiguous(), singer,
                                       fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=utt,
                                       wav16_float=None if wav16f is None else wav16f[None].contiguous(),
-                                      pcm16=pcm16, key_shift=key_shift)
+                                      pcm16=pcm16, key_shift=key_shift,
+                                      **({} if k_step is None else dict(k_step=k_step)))
     return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                  f0_method="parselmouth", pcm16=False, key_shift=0.0):
+                  f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
     list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
     pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
@@ -107,7 +134,7 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
     sid = int(singers[singer_name])
     wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), wavs16_float=w16f,
                                             fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16,
-                                            key_shift=key_shift)
+                                            key_shift=key_shift, **({} if k_step is None else dict(k_step=k_step)))
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
     return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
@@ -132,6 +159,12 @@ def build_parser():
     ap.add_argument("--fast", action="store_true", help="PLMS (fast_inference=True) instead of DDPM-1000")
     ap.add_argument("--speedup", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--k-step", type=int, default=None, metavar="K",
+                    help="shallow diffusion (Diff-SVC's k_step): noise the source's own mel forward to step K and "
+                         "denoise from there instead of from pure noise (1..1000; with and without --fast)")
+    ap.add_argument("--resynth", action="store_true",
+                    help="copy-synthesis: each file's own mel through the vocoder alone (judges a vocoder checkpoint; "
+                         "needs no mapper or content checkpoint); output gen/<wav stem>_resynth.wav")
     ap.add_argument("--mapper-ckpt", default=None)
     ap.add_argument("--vocoder-ckpt", default=None)
     ap.add_argument("--whisper-ckpt", default=None)
@@ -167,6 +200,23 @@ def main(argv=None):
     cfg = C.load_config(args.config) if args.config else C.load_config()
     mapper = args.mapper_ckpt or getattr(cfg, "svc_model_path", None)
     vocoder = args.vocoder_ckpt or getattr(cfg, "vocoder_model_path", None)
+    if args.resynth:
+        if not args.wav:
+            ap.error("--resynth needs --wav")
+        if args.out and len(args.wav) > 1:
+            raise SystemExit("--out names one output file: omit it when converting several files")
+        print("Loading vocoder...", flush=True)
+        engine = build_vocoder_engine(cfg, args.device, vocoder, args.random_weights, args.seed)
+        for path, (pcm, _) in zip(args.wav, resynth_files(engine, cfg, args.wav)):
+            out = args.out or os.path.join("gen", f"{os.path.splitext(os.path.basename(path))[0]}_resynth.wav")
+            A.write_wav_pcm16(out, pcm, cfg.fs)
+            print("Saving", out, flush=True)
+        engine.close()
+        return 0
+    try:
+        check_k_step(args.k_step, cfg)
+    except ValueError as exc:
+        ap.error(f"--k-step: {exc}")
     print("Loading mapper and vocoder...", flush=True)
     hubert = args.hubert_ckpt or getattr(cfg, "contentVec_model", None)
     engine = build_engine(cfg, args.device, mapper, vocoder, args.whisper_ckpt, args.random_weights, args.seed,
@@ -187,10 +237,10 @@ def main(argv=None):
     dev = f"cuda:{args.device}"
     if len(args.wav) == 1:
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
-                                f0_method=args.f0_method, pcm16=True, key_shift=args.key)]
+                                f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step)]
     else:
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
-                                f0_method=args.f0_method, pcm16=True, key_shift=args.key)
+                                f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step)
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
     for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU

@@ -28,7 +28,7 @@ from dataclasses import dataclass
 
 import torch
 
-from .runtime import SVCEngine, mel_frames
+from .runtime import SVCEngine, check_k_step, mel_frames
 
 WHISPER_WINDOW = 478720       # 16 kHz samples per long-input window (29.92 s)
 WINDOW_MEL_FRAMES = 2805      # = 1496 encoder frames * 15 / 8
@@ -211,17 +211,25 @@ class SVCPipeline:
         return self._side
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
-                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0):
+                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
         Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
         save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`.
-        key_shift: semitones on top of the shift to the singer's median, a scalar or one per clip (shift_f0)."""
+        key_shift: semitones on top of the shift to the singer's median, a scalar or one per clip (shift_f0).
+        k_step (shallow diffusion; None: the full schedule from noise, the call as before): the sampler starts from the
+        source's own mel noised to level k_step - 1 and denoises from there (SVCEngine.diffsvc_sample(k_step, mel_src));
+        x_T is not used then."""
+        k_step = self._check_k_step(k_step)
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
-                                 wav16_float, pcm16, key_shift)
+                                 wav16_float, pcm16, key_shift, k_step)
+
+    def _check_k_step(self, k_step):
+        """k_step validated against the engine's schedule (ValueError before any device work); None stays None."""
+        return None if k_step is None else check_k_step(k_step, getattr(self.engine, "cfg", None))
 
     def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
-                 pcm16=False, key_shift=0.0):
+                 pcm16=False, key_shift=0.0, k_step=None):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -241,15 +249,19 @@ class SVCPipeline:
         for t in (mel, energy, f0):
             t.record_stream(main)
         cond = e.condition(content, f0, energy, singer)
-        if utt_ids is None and x_T is None:
+        if utt_ids is None and (x_T is None or k_step is not None):
             utt_ids = torch.arange(wav24.shape[0], device=wav24.device, dtype=torch.int32)
-        x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, x_T=x_T, noise=noise, seed=seed,
-                              utt_ids=utt_ids)
+        if k_step is None:
+            x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, x_T=x_T, noise=noise,
+                                  seed=seed, utt_ids=utt_ids)
+        else:  # mel was computed on the side stream: joined and recorded for this one above
+            x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, noise=noise, seed=seed,
+                                  utt_ids=utt_ids, k_step=k_step, mel_src=mel)
         wav = e.bigvgan(x0)
         return ConvertResult(wav=wav, mel=mel, f0=f0, x0=x0, pcm=e.pcm16(wav) if pcm16 else None)
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0):
+                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -260,7 +272,10 @@ class SVCPipeline:
         bucketed=True instead runs one batch per distinct length.
         pcm16=True: each waveform comes back as save_audio's samples instead, int16 [T_i*hop + 2*(fs//20)]
         (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak).
-        key_shift: semitones, a scalar or one per utterance (shift_f0)."""
+        key_shift: semitones, a scalar or one per utterance (shift_f0).
+        k_step: shallow diffusion for the whole batch, as in convert()."""
+        k_step = self._check_k_step(k_step)
+        shallow = {} if k_step is None else dict(k_step=k_step)
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
             raise ValueError("convert_many: wavs24, wavs16, singers (and wavs16_float) must have one entry per utterance")
@@ -269,7 +284,7 @@ class SVCPipeline:
         if not bucketed:
             return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float,
                                        fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=ids,
-                                       pcm16=pcm16, **(dict(key_shift=key_shift) if shifted else {}))
+                                       pcm16=pcm16, **(dict(key_shift=key_shift) if shifted else {}), **shallow)
         ks = key_shift.tolist() if hasattr(key_shift, "tolist") else key_shift
         ks = [float(k) for k in ks] if isinstance(ks, (list, tuple)) else [float(ks)] * n
         buckets = {}
@@ -288,7 +303,7 @@ class SVCPipeline:
             uid = torch.tensor([ids[i] for i in idx], device=dev, dtype=torch.int32)
             res = self.convert(w24, w16, sing, fast_inference=fast_inference, speedup=speedup, seed=seed,
                                utt_ids=uid, wav16_float=w16f, pcm16=pcm16,
-                               **(dict(key_shift=[ks[i] for i in idx]) if shifted else {}))
+                               **(dict(key_shift=[ks[i] for i in idx]) if shifted else {}), **shallow)
             for j, i in enumerate(idx):
                 out[i] = res.pcm[j] if pcm16 else res.wav[j]
         return out
@@ -354,18 +369,20 @@ class SVCPipeline:
         return out
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                       utt_ids=None, pcm16=False, key_shift=0.0):
+                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
         [T_b * hop + 2 * (fs // 20)] (svc_pcm16 with the same lengths). Each clip's F0 moves onto its own singer's
-        median (shift_f0), then up by key_shift semitones (a scalar or one per clip)."""
+        median (shift_f0), then up by key_shift semitones (a scalar or one per clip). k_step: shallow diffusion, as in
+        convert(): each clip starts from its own mel, noised with its own utterance id's draw."""
+        k_step = self._check_k_step(k_step)
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                                        pcm16, key_shift)
+                                        pcm16, key_shift, k_step)
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
-                      float16k=None, key_shift=0.0):
+                      float16k=None, key_shift=0.0, k_step=None):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
@@ -373,16 +390,18 @@ class SVCPipeline:
         the configuration names a HuBERT content type (wants_float16k); False: HuBERT is fed Whisper's int16-grid rows.
         Without a HuBERT type and with None or False, load_batch is called without the keyword."""
         from . import audio as A
+        k_step = self._check_k_step(k_step)
         if wants_float16k(self.engine.cfg) if float16k is None else float16k:
             wavs24, wavs16, wavs16_float = A.load_batch(sources, self.engine.cfg.fs, self.engine, float16k=True)
         else:
             wavs24, wavs16 = A.load_batch(sources, self.engine.cfg.fs, self.engine)
             wavs16_float = None
         return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float, fast_inference=fast_inference,
-                                   speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift)
+                                   speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift,
+                                   **({} if k_step is None else dict(k_step=k_step)))
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                        pcm16=False, key_shift=0.0):
+                        pcm16=False, key_shift=0.0, k_step=None):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -405,7 +424,9 @@ class SVCPipeline:
         sing = torch.tensor([int(s) for s in singers], device=dev, dtype=torch.int32)
         cond = e.condition(content, f0, energy, sing)
         uid = torch.tensor(ids, device=dev, dtype=torch.int32)
-        x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=uid, frames=T_b)
+        shallow = {} if k_step is None else dict(k_step=k_step, mel_src=mel)  # mel: joined and recorded above
+        x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=uid, frames=T_b,
+                              **shallow)
         wav = e.bigvgan(x0, frames=T_b)
         hop = e.cfg.hop_length
         if pcm16:
@@ -413,3 +434,16 @@ class SVCPipeline:
             sil2 = pcm.shape[1] - wav.shape[1]  # both silences
             return [pcm[i, :T_b[i] * hop + sil2] for i in range(n)]
         return [wav[i, :T_b[i] * hop] for i in range(n)]
+
+    def resynthesize(self, wav24, n_samples=None):
+        """Copy-synthesis through the vocoder alone (how a vocoder checkpoint is judged on its own): wav24 f32 [B, N]
+        -> mel_energy -> mel_normalize -> bigvgan -> wav f32 [B, T * hop]; no content encoder, conditioner or sampler
+        runs, and the engine needs only its vocoder. n_samples (ragged batch, host ints [B]): clip b is
+        wav24[b, :n_samples[b]] and its waveform mel_frames(n_samples[b]) * hop samples, zeros after."""
+        e = self.engine
+        with e.lock:
+            frames = None
+            if n_samples is not None:
+                frames = [mel_frames(int(k), e.cfg.n_fft, e.cfg.hop_length) for k in n_samples]
+            mel, _ = e.mel_energy(wav24, n_samples=n_samples)
+            return e.bigvgan(e.mel_normalize(mel, frames=frames), frames=frames)

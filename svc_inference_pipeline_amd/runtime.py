@@ -55,6 +55,20 @@ def mel_frames(n_samples, n_fft=1024, hop=256):
     return (n_samples + (n_fft - hop) - n_fft) // hop + 1
 
 
+def check_k_step(k_step, cfg=None):
+    """Shallow diffusion's k_step as an int in [1, steps] (steps: the length of cfg.mapper's noise schedule; no upper
+    bound where cfg has no mapper section), else ValueError before any device work; None (the full schedule) stays
+    None."""
+    if k_step is None:
+        return None
+    mapper = getattr(cfg, "mapper", None)
+    steps = len(noise_schedule(mapper)) if mapper is not None else None
+    ok = isinstance(k_step, (int, np.integer)) and not isinstance(k_step, bool)
+    if not ok or k_step < 1 or (steps is not None and k_step > steps):
+        raise ValueError(f"k_step {k_step!r}: an integer in [1, {steps if steps is not None else 'steps'}]")
+    return int(k_step)
+
+
 def check_supported(cfg):
     """Reject configurations the native path does not implement, before any device work (raise ValueError)."""
     merge = getattr(cfg.mapper, "merge_mode", "add")
@@ -160,6 +174,10 @@ class SVCEngine:
             self._add("stats.mel_max", st["mel_max"])
             self.target_f0_median = st["target_f0_median"]
         if vocoder_state is not None:
+            if mapper_state is None:  # copy-synthesis (mel_normalize + bigvgan) needs the mel statistics alone
+                st = load_stats(cfg)
+                self._add("stats.mel_min", st["mel_min"])
+                self._add("stats.mel_max", st["mel_max"])
             self._add_state("vocoder.", vocoder_state)
             self._add("vocoder.fade_out", W.fade_out_table(20 * cfg.hop_length).numpy())
         _lib.call("svc_ctx_finalize", self._ctx)
@@ -393,17 +411,44 @@ class SVCEngine:
                   int(t), _ptr(eps), _stream())
         return eps
 
+    def mel_normalize(self, mel, frames=None):
+        """normalize_mel_channel (utils/acoustic_feature_extraction.py:75-80; not clamped): log-mel f32 [B, T, n_mel]
+        as mel_energy returns it -> f32 [B, T, n_mel] in the sampler's and the vocoder's normalised range. frames
+        (ragged batch, host ints [B]): rows past an utterance's frames come back as zeros."""
+        B, T, _ = mel.shape
+        out = torch.empty_like(mel, memory_format=torch.contiguous_format)
+        _lib.call("svc_mel_normalize", self._ctx, _ptr(mel.contiguous()), B, T,
+                  _host_lengths(frames, B, ctypes.c_int32), _ptr(out), _stream())
+        return out
+
     def diffsvc_sample(self, cond, fast_inference=False, speedup=10, x_T=None, noise=None, seed=0, utt_ids=None,
-                       frames=None):
+                       frames=None, k_step=None, mel_src=None, x_start=None):
         """svc_model_inference (modules/diffsvcrepo_inference.py:154-240) -> normalised mel x_0 f32 [B, T, n_mel].
-        frames (ragged batch, host ints [B]): utterance b's mel frames; its rows past them come back as zeros."""
+        frames (ragged batch, host ints [B]): utterance b's mel frames; its rows past them come back as zeros.
+        k_step (shallow diffusion, Diff-SVC's k_step; None: the whole schedule from x_T, the call as before): start
+        at noise level k_step - 1 from exactly one of mel_src (the source's un-normalised log-mel [B, T, n_mel]:
+        normalised and noised forward on the device, keyed by utt_ids) and x_start (an already noised state); DDPM
+        `noise` is then [k_step, B*T*n_mel] (svc_diffsvc_sample_from)."""
         B, T, _ = cond.shape
+        k_step = check_k_step(k_step, self.cfg)
+        if k_step is None and (mel_src is not None or x_start is not None):
+            raise ValueError("diffsvc_sample: mel_src / x_start need k_step")
+        if k_step is not None and (x_T is not None or (mel_src is None) == (x_start is None)):
+            raise ValueError("diffsvc_sample: k_step takes exactly one of mel_src and x_start (and no x_T)")
         x0 = torch.empty(B, T, self.cfg.mapper.n_mel, device=cond.device, dtype=torch.float32)
-        if utt_ids is None and (x_T is None or (noise is None and not fast_inference)):
+        if utt_ids is None and ((x_T is None and x_start is None) or (noise is None and not fast_inference)):
             # device noise (x_T, and DDPM's per-step z) is keyed by utterance id: default to batch positions
             utt_ids = torch.arange(B, device=cond.device, dtype=torch.int32)
         uid = utt_ids.to(torch.int32).contiguous() if utt_ids is not None else None
         mode = MODE_PLMS if fast_inference else MODE_DDPM
+        if k_step is not None:
+            _lib.call("svc_diffsvc_sample_from", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32),
+                      mode, int(speedup), k_step,
+                      _ptr(mel_src.contiguous()) if mel_src is not None else None,
+                      _ptr(x_start.contiguous()) if x_start is not None else None,
+                      _ptr(noise.contiguous()) if noise is not None else None, ctypes.c_uint64(seed), _ptr(uid),
+                      _ptr(x0), _stream())
+            return x0
         _lib.call("svc_diffsvc_sample", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32), mode,
                   int(speedup),
                   _ptr(x_T.contiguous()) if x_T is not None else None,
