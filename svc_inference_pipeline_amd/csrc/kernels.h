@@ -46,7 +46,9 @@ int gate_ws(const ConvGemmArgs& a, const EpiArgs& e, hipStream_t s);
 int gate_ws_pack(const f16* W, int ldw, f16* Wf, hipStream_t s);
 size_t gate_ws_pack_elems();
 int res_proj(const f16* g, const f16* Wf, const float* bias, const float* sub, const float* add, float div, f16* hi,
-             f16* lo, int M, bool bf16, int lanes_cap, hipStream_t s);
+             f16* lo, int M, bool bf16, int lanes_cap, bool store_lo, hipStream_t s);
+extern unsigned long long* res_proj_stamps;
+int res_proj_nstamp();
 int res_proj_pack(const f16* W, int ldw, f16* Wf, hipStream_t s);
 size_t res_proj_pack_elems();
 int mel_proj(const f16* x, int ldx, const f16* Wf, const float* bias, const float* add, f16* hi, f16* lo, int M,

@@ -437,8 +437,12 @@ extern "C" svc_status svc_gemm_bench(int M, int N, int Cin, int taps, int epi_ki
   size_t flush_bytes = (size_t)1 << 30;
   if (const char* fm = getenv("SVC_BENCH_FLUSH_MB")) flush_bytes = (size_t)atoi(fm) << 20;  // (bench tool only)
   if (cold) SVC_HIP_CHECK(hipMalloc(&flush, flush_bytes));
+  // (bench tool only) res_proj's row lanes: -2 one workgroup per CU (the one-stream sampler's), 0 3/8 of the CUs
+  const int rp_lanes = getenv("SVC_BENCH_RP_LANES") ? atoi(getenv("SVC_BENCH_RP_LANES")) : 0;
+  const bool rp_lo = !getenv("SVC_BENCH_RP_NOLO");  // (bench tool only) the form without the lo store
   auto run = [&]() {
-    if (variant == 30) return res_proj(X, Wf, bias, bias, bias, e.acc_div, Y, reinterpret_cast<f16*>(R), M, false, 0, 0);
+    if (variant == 30)
+      return res_proj(X, Wf, bias, bias, bias, e.acc_div, Y, reinterpret_cast<f16*>(R), M, false, rp_lanes, rp_lo, 0);
     if (variant == 20 || variant == 24) return conv_gemm4(a, e, zero_page(), 0, variant == 24);
     if (variant == 40) return gate_ws(a, e, 0);
     return conv_gemm3(a, e, zero_page(), variant - 10, 0);
@@ -453,6 +457,27 @@ extern "C" svc_status svc_gemm_bench(int M, int N, int Cin, int taps, int epi_ki
     gate_ws_stamps = ds;
     for (int w = 0; w < 3 && !st; ++w) st = run();  // the last launch's stamps remain
     gate_ws_stamps = nullptr;
+    SVC_HIP_CHECK(hipDeviceSynchronize());
+    std::vector<unsigned long long> hs(n);
+    SVC_HIP_CHECK(hipMemcpy(hs.data(), ds, n * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(ds);
+    if (FILE* f = fopen(sp, "wb")) {
+      fwrite(hs.data(), 8, n, f);
+      fclose(f);
+    }
+  }
+  if (const char* sp = variant == 30 ? getenv("SVC_RP_STAMPS") : nullptr) {  // (bench tool only) ramp / steady / drain
+    unsigned long long* ds = nullptr;
+    const size_t n = (size_t)1024 * res_proj_nstamp();  // (at most 2 x 512 row lanes' workgroups)
+    SVC_HIP_CHECK(hipMalloc(&ds, n * 8));
+    SVC_HIP_CHECK(hipMemset(ds, 0, n * 8));
+    SVC_HIP_CHECK(hipDeviceSynchronize());
+    res_proj_stamps = ds;
+    for (int w = 0; w < 3 && !st; ++w) {  // the last launch's stamps remain
+      if (cold) SVC_HIP_CHECK(hipMemsetAsync(flush, w, flush_bytes, 0));  // (operands from HBM, as in the sampler)
+      st = run();
+    }
+    res_proj_stamps = nullptr;
     SVC_HIP_CHECK(hipDeviceSynchronize());
     std::vector<unsigned long long> hs(n);
     SVC_HIP_CHECK(hipMemcpy(hs.data(), ds, n * 8, hipMemcpyDeviceToHost));

@@ -3,8 +3,9 @@
 res_proj_kernel: its ring waits (rp_wait_case) count this wave's vector-memory operations by hand; a compiler spill to
 scratch would add loads / stores the count does not know about, and it must stay <= 104 VGPRs to co-reside with the
 other sampler stream's gate GEMM (res_proj.hip). gate_ws_kernel: its first waves' vmcnt waits count the ring DMAs by
-hand (no scratch allowed either) and two waves per SIMD need <= 256 registers.
-Usage: check_kernel_resources.py REMARKS_FILE KERNEL_SUBSTRING MAX_VGPRS"""
+hand (no scratch allowed either) and two waves per SIMD need <= 256 registers. res_proj_ws_kernel (the loader-wave form,
+alone on the chip) and the stamped diagnostics instances: no scratch, two waves per SIMD.
+Usage: check_kernel_resources.py REMARKS_FILE KERNEL_REGEX MAX_VGPRS (the regex is searched in the mangled name)"""
 import re
 import sys
 
@@ -17,7 +18,7 @@ def main():
     bad = []
     for b in blocks:
         fn = b.split()[0]
-        if name not in fn:
+        if not re.search(name, fn):
             continue
         seen += 1
         get = lambda k: int(re.search(k + r": (\d+)", b).group(1))
