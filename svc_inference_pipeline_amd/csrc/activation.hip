@@ -46,15 +46,12 @@ __device__ __forceinline__ void act_run(__amdgpu_buffer_rsrc_t rx, __amdgpu_buff
   // the next block's rows are loaded while this block computes (f32: 106 registers, launches 3 % faster, r04u;
   // f16 as converted pairs was 2-3 % slower, r04u; as raw words, 98 registers = 4 waves per SIMD instead of 5, its
   // launches are 5-8 % faster, profiles/r06_ab/r06g_act_f16_prefetch.txt)
-  constexpr bool PF = true;
   f32x2 xw[P + 10], sw[2 * P + 10];
-  XR xn[PF ? P : 1];
+  XR xn[P];
 #pragma unroll
   for (int k = 0; k < 10; ++k) xw[k] = xl(t0 - 5 + k);
-  if constexpr (PF) {
 #pragma unroll
-    for (int k = 0; k < P; ++k) xn[k] = xlr(t0 + 5 + k);
-  }
+  for (int k = 0; k < P; ++k) xn[k] = xlr(t0 + 5 + k);
 #pragma unroll
   for (int i = 0; i < 10; ++i) sw[i] = s_win(xw, i);
   if (EDGE) {
@@ -68,16 +65,11 @@ __device__ __forceinline__ void act_run(__amdgpu_buffer_rsrc_t rx, __amdgpu_buff
   }
   for (int t = t0; t < t_end; t += P) {
     const uint32_t xrow = xo + (uint32_t)(t + 5) * xs, yrow = yo + (uint32_t)t * ys;
-    if constexpr (PF) {
 #pragma unroll
-      for (int k = 0; k < P; ++k) xw[10 + k] = act_cvt<TX>(xn[k]);
-      if (t + P < t_end) {
+    for (int k = 0; k < P; ++k) xw[10 + k] = act_cvt<TX>(xn[k]);
+    if (t + P < t_end) {
 #pragma unroll
-        for (int k = 0; k < P; ++k) xn[k] = EDGE ? xlr(t + P + 5 + k) : act_load_raw<TX>(rx, xrow, (P + k) * xs);
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < P; ++k) xw[10 + k] = EDGE ? xl(t + 5 + k) : act_load<TX>(rx, xrow, k * xs);
+      for (int k = 0; k < P; ++k) xn[k] = EDGE ? xlr(t + P + 5 + k) : act_load_raw<TX>(rx, xrow, (P + k) * xs);
     }
     // output p needs s up to index 2p+11, i.e. x up to window row 10+p
 #pragma unroll

@@ -16,7 +16,9 @@ struct AmpConvArgs {
   const int* tv = nullptr;  // ragged batches: utterance b has min(L, tv[b] * tv_mul) rows (NULL = all L)
   int tv_mul = 1;
   const f16* x16 = nullptr;  // when set, the activation input is this f16 tensor instead of x (an AMPBlock1 intermediate)
-  bool noact = false;  // x16 is the conv's input itself (C = 48 / 96 / 192): the plain conv, no SnakeBeta; the combined up-sampling
+  // x16 is the conv's input itself (C = 48 / 96 / 192): the plain conv, no SnakeBeta. Its one caller is svc_bigvgan's
+  // combined rate-2 up-sampling (VStage::upc, k = 3, d = -1).
+  bool noact = false;
   int dbg = 0;  // (diagnostics, SVC_AMP_DBG) 1 / 2 / 4: skip the activation / conv MFMAs / epilogue; 8: register epilogue
 };
 

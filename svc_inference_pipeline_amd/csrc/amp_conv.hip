@@ -1,4 +1,4 @@
-// BigVGAN AMP-block convolution for small channel counts (C = 24 / 48 / 96, the late generator stages),
+// BigVGAN AMP-block convolution for small channel counts (C = 24 / 48 / 96 / 192, the late generator stages),
 // with the Activation1d that precedes it fused in (modules/bigvgan.py:424-431 AMPBlock1.forward:
 // xt = a1(x); xt = c1(xt); xt = a2(xt); xt = c2(xt); x = xt + x — Activation1d :234-307, SnakeBeta :146-159).
 //
@@ -45,13 +45,10 @@ struct AmpCfg {
   // C = 192: 8 waves on 2 x 4 (each 128 rows x 48 columns), one workgroup per CU (the image is 127-133 KiB).
   static constexpr bool WIDE = C >= 96;
   static constexpr int NT = C == 192 ? 512 : AMP_NT;    // threads
-#ifndef AMP_BT192
-#define AMP_BT192 256
-#endif
-  static constexpr int BT = C == 192 ? AMP_BT192 : (WIDE ? 256 : 512);
+  static constexpr int BT = WIDE ? 256 : 512;           // output rows per workgroup
   static constexpr int WN = C == 192 ? 4 : (WIDE ? 2 : 1), WM = NT / 64 / WN;  // wave grid: WM row x WN column blocks
   static constexpr int NPART = 4;                       // epilogue staging parts (row blocks of BT / NPART)
-  static constexpr int OCC = (C == 192 && BT == 256) ? 1 : 2;  // workgroups per CU (launch bound)
+  static constexpr int OCC = C == 192 ? 1 : 2;          // workgroups per CU (launch bound)
   static constexpr int MAXP = 32;                   // max conv padding (k-1)/2*d supported
   // f16 row stride (96 / 96 / 224 B). A K-step's ds_read_b128 mixes lanes of two taps (rows tap*d apart) and CPT
   // chunks per tap, so the bank pattern depends on the stride: modelled over k in {3,7,11}, d in {1,3,5} with the
@@ -165,6 +162,12 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
   const int rows = CF::BT + 2 * P;
   const int tap0 = p.d < 0 ? 2 * P : 0;
 
+  // The p.dbg tests below (diagnostics, SVC_AMP_DBG, never set in production) stay in the production kernel on
+  // purpose: its code generation rests on them. With them compiled out (a DIAG twin per form, dbg fixed at 0 here) the
+  // plain-conv instances go from 166 / 172 / 170 VGPRs (C = 48 / 96 / 192) to 255 / 174 / 182, C = 48 from 3 waves per
+  // SIMD to 2, and amp_conv<48,conv> runs 12 % slower (0.216 -> 0.243 ms per step), amp_conv<192,conv> 1 %. A
+  // sched_barrier where the tests stood left every register count as it was, and in a second measurement
+  // amp_conv<48,conv> was still 8 % slower (0.216 -> 0.234) (profiles/amp_diag_resources.txt, amp_diag_ab.txt).
   // ------------------------------------------------------------------ 1. SnakeBeta -> LDS (f16)
   if constexpr (NOACT) {
     if (!(p.dbg & 1)) {
@@ -386,30 +389,51 @@ __global__ __launch_bounds__((AmpCfg<C, NOACT>::NT), (AmpCfg<C, NOACT>::OCC)) vo
   }
 }
 
-template <int C, bool X16, bool NOACT = false>
-static int launch_amp(const AmpConvArgs& p, const EpiArgs& e, hipStream_t s) {
+// One instance of the kernel: its form (C, f16 input, plain conv), its profiler tag, and what the launcher needs of its
+// AmpCfg. AMP_INSTS names every instance, once.
+struct AmpInst {
+  int C;
+  bool x16, noact;
+  const char* tag;
+  void (*kernel)(AmpConvArgs, EpiArgs);
+  int NT, BT, LDA, STG_BYTES, LDS;
+};
+template <int C, bool X16, bool NOACT>
+constexpr AmpInst amp_inst(const char* tag) {
   using CF = AmpCfg<C, NOACT>;
-  if (int st = ensure_dyn_lds((const void*)amp_conv_kernel<C, X16, NOACT>, CF::LDS)) return st;
-  const int64_t grid = (int64_t)p.B * cdiv(p.L, CF::BT);
+  return {C, X16, NOACT, tag, amp_conv_kernel<C, X16, NOACT>, CF::NT, CF::BT, CF::LDA, CF::STG_BYTES, CF::LDS};
+}
+static constexpr AmpInst AMP_INSTS[] = {
+    amp_inst<24, true, false>("amp_conv<24,x16>"),   amp_inst<24, false, false>("amp_conv<24>"),
+    amp_inst<48, true, true>("amp_conv<48,conv>"),   amp_inst<48, true, false>("amp_conv<48,x16>"),
+    amp_inst<48, false, false>("amp_conv<48>"),      amp_inst<96, true, true>("amp_conv<96,conv>"),
+    amp_inst<96, true, false>("amp_conv<96,x16>"),   amp_inst<96, false, false>("amp_conv<96>"),
+    amp_inst<192, true, true>("amp_conv<192,conv>"), amp_inst<192, true, false>("amp_conv<192,x16>"),
+    amp_inst<192, false, false>("amp_conv<192>"),
+};
+
+static int launch_amp(const AmpInst& in, const AmpConvArgs& p, const EpiArgs& e, hipStream_t s) {
+  const int C = in.C;
+  const void* kernel = (const void*)in.kernel;
+  if (int st = ensure_dyn_lds(kernel, in.LDS)) return st;
+  const int64_t grid = (int64_t)p.B * cdiv(p.L, in.BT);
   SVC_REQUIRE(grid > 0 && grid < (1ll << 31), "amp_conv: bad grid");
   const double elems = (double)p.B * p.L * C;
   // algorithmic bytes: x in (f32 or f16), output out (f32 and/or f16), epilogue operands in (f32)
   const double bytes =
-      elems * ((X16 ? 2.0 : 4.0) + (e.out32 ? 4 : 0) + (e.out16 ? 2 : 0) + (e.add_row ? 4 : 0) + (e.acc32 ? 4 : 0));
-  const char* tag = NOACT ? (C == 48 ? "amp_conv<48,conv>" : (C == 96 ? "amp_conv<96,conv>" : "amp_conv<192,conv>"))
-                   : X16 ? (C == 24 ? "amp_conv<24,x16>" : (C == 48 ? "amp_conv<48,x16>" : (C == 96 ? "amp_conv<96,x16>" : "amp_conv<192,x16>")))
-                         : (C == 24 ? "amp_conv<24>" : (C == 48 ? "amp_conv<48>" : (C == 96 ? "amp_conv<96>" : "amp_conv<192>")));
-  const int tok = prof_begin(tag, 2.0 * elems * C * p.k, bytes, s);
+      elems * ((in.x16 ? 2.0 : 4.0) + (e.out32 ? 4 : 0) + (e.out16 ? 2 : 0) + (e.add_row ? 4 : 0) + (e.acc32 ? 4 : 0));
+  const int tok = prof_begin(in.tag, 2.0 * elems * C * p.k, bytes, s);
   // the activation image needs BT + 2P rows, not BT + 2 MAXP: sized per launch, C = 48 fits 5 workgroups per CU
   // (instead of 4) for every conv with P <= 15
   const int P = (p.k - 1) / 2 * (p.d < 0 ? -p.d : p.d);
-  const int rows = CF::BT + 2 * P, run = amp_run_len(C, rows, CF::NT);
-  const int img_rows = NOACT ? rows : (rows + run - 1) / run * run;
-  const int lds = std::max(img_rows * CF::LDA * 2, CF::STG_BYTES);
+  const int rows = in.BT + 2 * P, run = amp_run_len(C, rows, in.NT);
+  const int img_rows = in.noact ? rows : (rows + run - 1) / run * run;
+  const int lds = std::max(img_rows * in.LDA * 2, in.STG_BYTES);
   static const int dbg = getenv("SVC_AMP_DBG") ? atoi(getenv("SVC_AMP_DBG")) : 0;
   AmpConvArgs pa = p;
   pa.dbg = dbg;
-  hipLaunchKernelGGL((amp_conv_kernel<C, X16, NOACT>), dim3((unsigned)grid), dim3(CF::NT), lds, s, pa, e);
+  void* args[] = {&pa, const_cast<EpiArgs*>(&e)};
+  (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(in.NT), args, lds, s);  // (a failure: SVC_LAUNCH_CHECK)
   prof_end(tok, s);
   SVC_LAUNCH_CHECK();
   return SVC_OK;
@@ -422,7 +446,10 @@ bool amp_conv_supported(int C, int k, int d) {
 
 // act + conv + epilogue; e uses out32 / out16 / add_row / acc32 with leading dimension C (contiguous rows)
 int amp_conv(const AmpConvArgs& p, int C, const EpiArgs& e, hipStream_t s) {
-  SVC_REQUIRE(amp_conv_supported(C, p.k, p.d) && (!p.noact || ((C == 48 || C == 96 || C == 192) && p.x16)) && (p.noact || p.d > 0),
+  const AmpInst* in = nullptr;
+  for (const AmpInst& i : AMP_INSTS)
+    if (i.C == C && i.x16 == (p.x16 != nullptr) && i.noact == p.noact) in = &i;
+  SVC_REQUIRE(in && amp_conv_supported(C, p.k, p.d) && (p.noact || p.d > 0),
               "amp_conv: C=%d k=%d d=%d noact=%d unsupported", C, p.k, p.d, (int)p.noact);
   SVC_REQUIRE(p.L >= 1 && p.Kpad >= p.k * C && p.Kpad % 32 == 0, "amp_conv: L=%d Kpad=%d", p.L, p.Kpad);
   SVC_REQUIRE((!e.out32 || e.ld32 == C) && (!e.out16 || e.ld16 == C) && (!e.add_row || e.ld_add_row == C) &&
@@ -449,21 +476,7 @@ int amp_conv(const AmpConvArgs& p, int C, const EpiArgs& e, hipStream_t s) {
     if (f.out16) f.out16 += off;
     if (f.acc32) f.acc32 += off;
     if (f.add_row) f.add_row += off;
-    int st;
-    if (C == 24)
-      st = q.x16 ? launch_amp<24, true>(q, f, s) : launch_amp<24, false>(q, f, s);
-    else if (C == 48 && q.noact)
-      st = launch_amp<48, true, true>(q, f, s);
-    else if (C == 48)
-      st = q.x16 ? launch_amp<48, true>(q, f, s) : launch_amp<48, false>(q, f, s);
-    else if (C == 96 && q.noact)
-      st = launch_amp<96, true, true>(q, f, s);
-    else if (C == 96)
-      st = q.x16 ? launch_amp<96, true>(q, f, s) : launch_amp<96, false>(q, f, s);
-    else if (q.noact)
-      st = launch_amp<192, true, true>(q, f, s);
-    else
-      st = q.x16 ? launch_amp<192, true>(q, f, s) : launch_amp<192, false>(q, f, s);
+    const int st = launch_amp(*in, q, f, s);
     if (st) return st;
   }
   return SVC_OK;

@@ -26,8 +26,8 @@ done
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in base new; do
     if [ $lib = base ]; then L=$PWD/${BASE_LIB:-ab/libsvc_hip_base.so}; else L=$PWD/svc_inference_pipeline_amd/libsvc_hip.so; fi
-    SVC_HIP_LIB=$L timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $O/b_$lib.json 2> $O/b_$lib.err || exit $?
-    python3 - $O/b_$lib.json $lib <<'PY'
+    SVC_HIP_LIB=$L timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 > $O/b_${lib}_$r.json 2> $O/b_${lib}_$r.err || exit $?
+    python3 - $O/b_${lib}_$r.json $lib <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 k = d["kernels"]
