@@ -438,6 +438,40 @@ svc_status svc_op_plms_update(const float* e0, const float* e1, const float* e2,
 svc_status svc_op_ddpm_update(float* x, const float* eps, int B, int T, int C, float sra, float srm1, float c1,
                               float c2, float sigma, const float* z, uint64_t seed, const int32_t* utt_ids, int step,
                               void* x16, int ld16, int bf16, void* stream);
+/* The DiffSVC denoiser's steps one at a time, each through the launcher choice svc_diffsvc_eps / svc_diffsvc_sample
+ * make for it (stage_diffsvc.hip diffsvc_*), selected as there by the op-level context's kernel switches
+ * (svc_ctx_set_config(NULL, "tune.gate_ws" | "tune.gemm_variant" | "tune.res_proj" | "tune.diff_head" |
+ * "tune.sampler_streams")). C = 384 residual channels, n_mel = 100. Every pointer is a device pointer; 16-bit tensors
+ * are binary16, or bfloat16 bits with bf16 = 1 (the weights are then packed as bfloat16 too). Weights are f32 in the
+ * reference's layout and channel order and are packed per call as svc_ctx_finalize packs them. Arguments are checked
+ * before any HIP call (SVC_ERR_INVALID).
+ * gate: y16 [B*T][384] = sigmoid(g) * tanh(f), [g | f] = conv1d_k3(x16 [B*T][384]; w [768][384][3], bias [768],
+ * dilation dil in {1, 2, 4, 8}, zero padding per utterance) + cp16 [B*T][768]. tv (DEVICE int32 [B] or NULL):
+ * utterance b's input rows t >= tv[b] read as zero; every output row is written. */
+svc_status svc_op_diffsvc_gate(const void* x16, int B, int T, const float* w, const float* bias, const void* cp16,
+                               int dil, const int32_t* tv, int bf16, void* y16, void* stream);
+/* res: the split residual stream hi + lo [M][384] updated in place, v = ((hi + lo) - sub + g16 [M][384] w^T + bias) /
+ * sqrt(2) + add, hi = round16(v), lo = round16(v - hi); w [384][384] (the residual half of a layer's
+ * output_projection), bias / sub / add [384]. lanes_cap: res_proj's row lanes as the stage computes them (-2, 0 or a
+ * count), -1: the tiled GEMM. store_lo = 0 (res_proj only; the tiled GEMM always writes lo): lo is read, not written. */
+svc_status svc_op_diffsvc_res(const void* g16, int M, const float* w, const float* bias, const float* sub,
+                              const float* add, int store_lo, int lanes_cap, int bf16, void* hi, void* lo,
+                              void* stream);
+/* melpre: v = relu(x16 [M][104] (columns 100..103 zero) w^T + bias) + add into hi / lo [M][384]; w [384][100]. */
+svc_status svc_op_diffsvc_melpre(const void* x16, int M, const float* w, const float* bias, const float* add, int bf16,
+                                 void* hi, void* lo, void* stream);
+/* skipsum: s = (sum_l g16[l][row0 + r] w[l]^T + sum_l bias[l]) / sqrt(NL) for r < rows, g16 layer-major
+ * [NL][rows_total][384], w [NL][384][384] / bias [NL][384] the skip halves; s16 [rows][1152] = [hi | lo | hi]. */
+svc_status svc_op_diffsvc_skipsum(const void* g16, int NL, int rows_total, int row0, int rows, const float* w,
+                                  const float* bias, int bf16, void* s16, void* stream);
+/* head: eps [M][100] = relu(s wsp^T + bsp) wout^T + bout on split operands, s16 [M][1152] = [hi | lo | hi],
+ * wsp [384][384], wout [100][384]; one launch or two by "tune.diff_head". */
+svc_status svc_op_diffsvc_head(const void* s16, int M, const float* wsp, const float* bsp, const float* wout,
+                               const float* bout, int bf16, float* eps, void* stream);
+/* condproj: cp16 [NL][M][768] (layer-major, reference channel order) = cond [M][384] (f32, split into 16-bit
+ * hi + lo) w[l]^T + bias[l]; w [NL][768][384], bias [NL][768]. */
+svc_status svc_op_diffsvc_condproj(const float* cond, int M, int NL, const float* w, const float* bias, int bf16,
+                                   void* cp16, void* stream);
 /* live per-kernel timing: enable(1) clears and starts recording (hipEvents around each launch),
    read(idx, ...) synchronises and returns kernel idx's name, total ms, launches, algorithmic FLOPs/bytes;
    n_kernels receives the number of distinct kernels. */

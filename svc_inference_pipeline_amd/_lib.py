@@ -88,6 +88,17 @@ PROTOTYPES = {
                                    c_int, c_int, c_int, c_void_p]),
     "svc_op_ddpm_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                    c_void_p, c_uint64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "svc_op_diffsvc_gate": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                    c_void_p, c_void_p]),
+    "svc_op_diffsvc_res": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_void_p, c_void_p, c_void_p]),
+    "svc_op_diffsvc_melpre": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p]),
+    "svc_op_diffsvc_skipsum": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p]),
+    "svc_op_diffsvc_head": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p]),
+    "svc_op_diffsvc_condproj": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "svc_profile_enable": (c_int, [c_int]),
     "svc_profile_filter": (c_int, [ctypes.c_char_p]),
     "svc_profile_read": (c_int, [c_int, ctypes.c_char_p, c_int, ctypes.POINTER(c_double), ctypes.POINTER(c_int64),

@@ -234,6 +234,12 @@ int pack_conv1d(svc_ctx* c, PackedGemm& g, const float* w, const float* bias, in
 int pack_conv_transpose(svc_ctx* c, std::vector<PackedGemm>& phases, const float* v, const float* wn_g,
                         const float* bias, int Cin, int Cout, int k, int s, int pad);
 int pack_conv_transpose_comb(svc_ctx* c, VStage& S, const float* v, const float* wn_g, const float* bias);
+int pack_conv1d_opt(svc_ctx* c, PackedGemm& g, const float* w, const float* bias, int Cout, int Cin, int k, int Cp,
+                    int dil, int pad, int stride, bool split);
+std::vector<int> pair_perm(int C);
+int pack_skip_all(svc_ctx* c, PackedGemm& g, const float* const* ow, const float* const* ob, int C, int NL);
+int pack_cond_all(svc_ctx* c, PackedGemm& g, const float* const* cpw, const float* const* cpb, int C, int NL,
+                  int cond_sz);
 int build_features(svc_ctx* c);
 int build_whisper(svc_ctx* c);
 int build_hubert(svc_ctx* c);
@@ -242,6 +248,30 @@ int build_stats(svc_ctx* c);
 int build_vocoder(svc_ctx* c);
 // stage_diffsvc.hip
 int stage_frames(StageRing& ring, const int32_t* frames, int B, int T, hipStream_t s, const int** dev_out);
+// The denoiser's steps, one launcher choice each (denoise / project_cond run them; the svc_op_diffsvc_* entry points
+// run them one at a time). C: the residual channels; hi / lo: the split residual stream [B*T][C].
+// mel_preprocess + ReLU + add (the layer-0 diffusion projection) into hi / lo
+int diffsvc_melpre(const PackedGemm& melpre, const f16* x16, int ldx16, int n_mel, const float* add, f16* hi, f16* lo,
+                   int C, int B, int T, hipStream_t s);
+// dilated conv + conditioner projection (cp [B*T][2C], paired order) + gate into y16 [B*T][C]
+int diffsvc_gate(const PackedGemm& dil, const f16* x16, const f16* cp, f16* y16, int C, int B, int T, const int* tv,
+                 hipStream_t s);
+// res_proj's row lanes as the kernel switches give them, -1: the tiled GEMM
+int diffsvc_res_lanes();
+// (hi + lo) - sub + g16 @ W_res + b, / sqrt(2), + add, back into hi / lo in place; lanes_cap: diffsvc_res_lanes().
+// store_lo false (res_proj only; the tiled GEMM always writes lo): lo is read and not written
+int diffsvc_residual(const PackedGemm& outres, const f16* g16, const float* sub, const float* add, f16* hi, f16* lo,
+                     int C, int B, int T, int lanes_cap, bool store_lo, hipStream_t s);
+// sum over the NL layer-major gate outputs (layer stride g_ls elements) of rows `rows` / sqrt(NL) into s16
+// ([hi | lo | hi] of 3C when head_split, else C)
+int diffsvc_skipsum(const PackedGemm& skip_all, const f16* g16, size_t g_ls, int NL, f16* s16, int C, bool head_split,
+                    int rows, hipStream_t s);
+// relu(skip_projection) and output_projection: one launch (diff_head) where it fits, else two GEMMs through u16
+int diffsvc_head(const PackedGemm& skipproj, const PackedGemm& outproj, const f16* s16, f16* u16, float* eps, int C,
+                 int n_mel, bool head_split, int B, int T, hipStream_t s);
+// cond f32 [B*T][C] -> cond16 [hi | lo | hi] -> every layer's conditioner projection, layer-major (stride cp_ls)
+int diffsvc_condproj(const PackedGemm& cp_all, const float* cond, f16* cond16, f16* cp16, size_t cp_ls, int C,
+                     bool bf16, int B, int T, hipStream_t s);
 // ops.hip
 int op_ws(svc_ctx** tmp);
 

@@ -229,8 +229,8 @@ int pack_conv1d(svc_ctx* c, PackedGemm& g, const float* w, const float* bias, in
 }
 
 // Conv1d [Cout][Cin][k] (+ bias) packed for a split-fp16 operand when `split`, else as pack_conv1d
-static int pack_conv1d_opt(svc_ctx* c, PackedGemm& g, const float* w, const float* bias, int Cout, int Cin, int k,
-                           int Cp, int dil, int pad, int stride, bool split) {
+int pack_conv1d_opt(svc_ctx* c, PackedGemm& g, const float* w, const float* bias, int Cout, int Cin, int k, int Cp,
+                    int dil, int pad, int stride, bool split) {
   if (!split) return pack_conv1d(c, g, w, bias, Cout, Cin, k, Cp, dil, pad, stride);
   int st = pack_gemm_split3(
       c, g, Cout, Cin, [&](int n, int ci, int t) { return w[((int64_t)n * Cin + ci) * k + t]; },
@@ -317,10 +317,44 @@ int pack_conv_transpose_comb(svc_ctx* c, VStage& S, const float* v, const float*
 }
 
 // paired packing order (conv_gemm2 epilogue): packed n -> original channel ((n & 32) ? C : 0) + (n >> 6) * 32 + (n & 31)
-static std::vector<int> pair_perm(int C) {
+std::vector<int> pair_perm(int C) {
   std::vector<int> p(2 * C);
   for (int n = 0; n < 2 * C; ++n) p[n] = ((n & 32) ? C : 0) + (n >> 6) * 32 + (n & 31);
   return p;
+}
+
+// The DiffSVC skip sum: sum over layers of skip_l = g_l @ Wskip_l + bskip_l as ONE GEMM over the concatenated gate
+// outputs [g_0 .. g_{NL-1}] (K = NL * C): no per-layer f32 skip read-modify-write. ow[l] [C][C] / ob[l] [C]: the skip
+// half of layer l's output_projection (its rows C..2C-1, modules/diffsvc.py:229-231)
+int pack_skip_all(svc_ctx* c, PackedGemm& g, const float* const* ow, const float* const* ob, int C, int NL) {
+  return pack_gemm(
+      c, g, C, NL * C, NL * C, 1,
+      [&](int n, int ci, int) {
+        const int l = ci / C, k = ci % C;
+        return ow[l][(int64_t)n * C + k];
+      },
+      [&](int n) {
+        double b = 0;
+        for (int l = 0; l < NL; ++l) b += ob[l][n];
+        return (float)b;
+      });
+}
+
+// All NL conditioner projections (cpw[l] [2C][cond_sz], cpb[l] [2C]) as one GEMM in split-fp16 precision, each layer's
+// 2C columns in the paired order of its gate GEMM (pair_perm)
+int pack_cond_all(svc_ctx* c, PackedGemm& g, const float* const* cpw, const float* const* cpb, int C, int NL,
+                  int cond_sz) {
+  const std::vector<int> perm = pair_perm(C);
+  return pack_gemm_split3(
+      c, g, NL * 2 * C, cond_sz,
+      [&](int n, int ci, int) {
+        int layer = n / (2 * C), o = perm[n % (2 * C)];
+        return cpw[layer][(int64_t)o * cond_sz + ci];
+      },
+      [&](int n) {
+        int layer = n / (2 * C), o = perm[n % (2 * C)];
+        return cpb[layer][o];
+      });
 }
 
 // ---------------------------------------------------------------------------- finalize: whisper
@@ -694,35 +728,20 @@ int build_mapper(svc_ctx* c) {
     opw_l[i] = ow;
     opb_l[i] = ob;
   }
-  // sum over layers of skip_i = g_i @ Wskip_i + bskip_i is ONE GEMM over the concatenated gate outputs
-  // [g_0 .. g_{L-1}] (K = L*C): no per-layer f32 skip read-modify-write
-  st = pack_gemm(
-      c, c->skip_all, C, NL * C, NL * C, 1,
-      [&](int n, int ci, int) {
-        const int l = ci / C, k = ci % C;
-        return opw_l[l]->host[(int64_t)(C + n) * C + k];
-      },
-      [&](int n) {
-        double b = 0;
-        for (int l = 0; l < NL; ++l) b += opb_l[l]->host[C + n];
-        return (float)b;
-      });
-  if (st) return st;
+  // sum over layers of skip_i = g_i @ Wskip_i + bskip_i is ONE GEMM over the concatenated gate outputs (pack_skip_all)
+  std::vector<const float*> ow_h(NL), ob_h(NL), cpw_h(NL), cpb_h(NL);
+  for (int i = 0; i < NL; ++i) {
+    ow_h[i] = opw_l[i]->host + (size_t)C * C;
+    ob_h[i] = opb_l[i]->host + C;
+    cpw_h[i] = cpw[i]->host;
+    cpb_h[i] = cpb[i]->host;
+  }
+  if ((st = pack_skip_all(c, c->skip_all, ow_h.data(), ob_h.data(), C, NL))) return st;
   const int cond_sz = (int)cpw[0]->shape[1];
   // all 20 conditioner projections as one GEMM (loop-invariant over diffusion steps: hoisted), in split-fp16
   // precision: it runs once per batch, and its rounding is the largest single denoiser-side term of the
   // mel-L1 error (precision sweep)
-  st = pack_gemm_split3(
-      c, c->cp_all, NL * 2 * C, cond_sz,
-      [&](int n, int ci, int) {
-        int layer = n / (2 * C), o = perm[n % (2 * C)];
-        return cpw[layer]->host[(int64_t)o * cond_sz + ci];
-      },
-      [&](int n) {
-        int layer = n / (2 * C), o = perm[n % (2 * C)];
-        return cpb[layer]->host[o];
-      });
-  if (st) return st;
+  if ((st = pack_cond_all(c, c->cp_all, cpw_h.data(), cpb_h.data(), C, NL, cond_sz))) return st;
   GETP(spw, q + "skip_projection.weight", C, C, 1);
   GETP(spb, q + "skip_projection.bias", C);
   GETP(opw, q + "output_projection.weight", nmel, C, 1);

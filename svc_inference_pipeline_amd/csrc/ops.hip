@@ -349,6 +349,214 @@ svc_status svc_op_ddpm_update(float* x, const float* eps, int B, int T, int C, f
   return ddpm_update(x, eps, (f16*)x16, ld16, B, T, C, a, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------- the DiffSVC denoiser's steps
+// Each entry packs its f32 weights as build_mapper does (finalize.hip), runs the step's helper of stage_diffsvc.hip
+// (the launcher choice denoise / project_cond make, by the op-level context's kernel switches) and frees the packs.
+// C = 384 residual channels, n_mel = 100 (rows of 104 halves), as the fragment-order kernels are built for.
+constexpr int OPD_C = 384, OPD_NMEL = 100, OPD_LDX = 104;
+
+namespace {
+// the operand format of the packs made inside the scope (svc_ctx::pack_bf16)
+struct PackFormat {
+  svc_ctx* c;
+  PackFormat(svc_ctx* ctx, int bf16) : c(ctx) { c->pack_bf16 = bf16 != 0; }
+  ~PackFormat() { c->pack_bf16 = false; }
+};
+// a packed weight set, its fragment-order copy and a scratch buffer, released after a stream sync
+struct OpPacks {
+  svc_ctx* c;
+  hipStream_t s;
+  std::vector<PackedGemm> g;
+  std::vector<void*> tmp;
+  OpPacks(svc_ctx* ctx, hipStream_t stream, int n) : c(ctx), s(stream), g(n) {}
+  int alloc(size_t bytes, void** out) {
+    SVC_HIP_CHECK(hipMalloc(out, bytes));
+    tmp.push_back(*out);
+    return SVC_OK;
+  }
+  ~OpPacks() {
+    (void)hipStreamSynchronize(s);
+    for (auto& p : g)
+      if (p.W) free_packed(c, p);
+    for (void* p : tmp) (void)hipFree(p);
+  }
+};
+// [rows][2C] 16-bit words between the reference's channel order and a gate GEMM's paired order (pair_perm): to_packed
+// dst[n] = src[perm[n]], else dst[perm[n]] = src[n]
+int permute_cp(const void* src, void* dst, size_t rows, int C, bool to_packed) {
+  const std::vector<int> perm = pair_perm(C);
+  std::vector<uint16_t> a(rows * 2 * C), b(rows * 2 * C);
+  SVC_HIP_CHECK(hipDeviceSynchronize());
+  SVC_HIP_CHECK(hipMemcpy(a.data(), src, a.size() * 2, hipMemcpyDeviceToHost));
+  for (size_t r = 0; r < rows; ++r)
+    for (int n = 0; n < 2 * C; ++n) {
+      if (to_packed) b[r * 2 * C + n] = a[r * 2 * C + perm[n]];
+      else b[r * 2 * C + perm[n]] = a[r * 2 * C + n];
+    }
+  SVC_HIP_CHECK(hipMemcpy(dst, b.data(), b.size() * 2, hipMemcpyHostToDevice));
+  return SVC_OK;
+}
+}  // namespace
+
+svc_status svc_op_diffsvc_gate(const void* x16, int B, int T, const float* w, const float* bias, const void* cp16,
+                               int dil, const int32_t* tv, int bf16, void* y16, void* stream) {
+  SVC_REQUIRE(x16 && w && bias && cp16 && y16 && B > 0 && T > 0, "op_diffsvc_gate: bad args");
+  SVC_REQUIRE(dil == 1 || dil == 2 || dil == 4 || dil == 8, "op_diffsvc_gate: dilation %d (1, 2, 4 or 8)", dil);
+  SVC_REQUIRE((int64_t)B * T * 2 * OPD_C * 2 < (1ll << 30), "op_diffsvc_gate: %d x %d rows", B, T);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = OPD_C;
+  PackFormat fmt(c, bf16);
+  OpPacks pk(c, s, 1);
+  PackedGemm& g = pk.g[0];
+  std::vector<float> wh, bh;
+  int st;
+  if ((st = pack_from_device(w, (size_t)2 * C * C * 3, bias, 2 * C, wh, bh))) return st;
+  const std::vector<int> perm = pair_perm(C);
+  if ((st = pack_conv1d(c, g, wh.data(), bh.data(), 2 * C, C, 3, C, dil, dil, 1, &perm))) return st;
+  void *wf, *cpp;
+  if ((st = pk.alloc(gate_ws_pack_elems() * sizeof(f16), &wf))) return st;  // gate_ws's fragment order, as build_mapper
+  g.Wfrag = reinterpret_cast<f16*>(wf);
+  if ((st = gate_ws_pack(g.W, g.Kpad, g.Wfrag, 0))) return st;
+  SVC_HIP_CHECK(hipStreamSynchronize(0));
+  if ((st = pk.alloc((size_t)B * T * 2 * C * sizeof(f16), &cpp))) return st;
+  if ((st = permute_cp(cp16, cpp, (size_t)B * T, C, true))) return st;
+  return diffsvc_gate(g, (const f16*)x16, (const f16*)cpp, (f16*)y16, C, B, T, tv, s);
+}
+
+svc_status svc_op_diffsvc_res(const void* g16, int M, const float* w, const float* bias, const float* sub,
+                              const float* add, int store_lo, int lanes_cap, int bf16, void* hi, void* lo,
+                              void* stream) {
+  SVC_REQUIRE(g16 && w && bias && sub && add && hi && lo && M > 0, "op_diffsvc_res: bad args");
+  SVC_REQUIRE(lanes_cap >= -2 && lanes_cap <= 512, "op_diffsvc_res: lanes_cap %d (-1 tiled GEMM, -2, 0 or a lane count)",
+              lanes_cap);
+  SVC_REQUIRE((int64_t)M * OPD_C * 2 < (1ll << 30), "op_diffsvc_res: %d rows", M);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = OPD_C;
+  PackFormat fmt(c, bf16);
+  OpPacks pk(c, s, 1);
+  PackedGemm& g = pk.g[0];
+  std::vector<float> wh, bh;
+  int st;
+  if ((st = pack_from_device(w, (size_t)C * C, bias, C, wh, bh))) return st;
+  if ((st = pack_conv1d(c, g, wh.data(), bh.data(), C, C, 1, C, 1, 0, 1))) return st;
+  void* wf;
+  if ((st = pk.alloc(res_proj_pack_elems() * sizeof(f16), &wf))) return st;
+  g.Wfrag = reinterpret_cast<f16*>(wf);
+  if ((st = res_proj_pack(g.W, g.Kpad, g.Wfrag, 0))) return st;
+  SVC_HIP_CHECK(hipStreamSynchronize(0));
+  return diffsvc_residual(g, (const f16*)g16, sub, add, (f16*)hi, (f16*)lo, C, 1, M, lanes_cap, store_lo != 0, s);
+}
+
+svc_status svc_op_diffsvc_melpre(const void* x16, int M, const float* w, const float* bias, const float* add, int bf16,
+                                 void* hi, void* lo, void* stream) {
+  SVC_REQUIRE(x16 && w && bias && add && hi && lo && M > 0, "op_diffsvc_melpre: bad args");
+  SVC_REQUIRE((int64_t)M * OPD_C * 2 < (1ll << 30), "op_diffsvc_melpre: %d rows", M);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = OPD_C;
+  PackFormat fmt(c, bf16);
+  OpPacks pk(c, s, 1);
+  PackedGemm& g = pk.g[0];
+  std::vector<float> wh, bh;
+  int st;
+  if ((st = pack_from_device(w, (size_t)C * OPD_NMEL, bias, C, wh, bh))) return st;
+  if ((st = pack_conv1d(c, g, wh.data(), bh.data(), C, OPD_NMEL, 1, OPD_LDX, 1, 0, 1))) return st;
+  if (g.Kpad == 128 && g.K <= 128) {  // mel_proj's shape, as build_mapper
+    void* wf;
+    if ((st = pk.alloc(mel_proj_pack_elems() * sizeof(f16), &wf))) return st;
+    g.Wfrag = reinterpret_cast<f16*>(wf);
+    if ((st = mel_proj_pack(g.W, g.Kpad, g.Wfrag, 0))) return st;
+    SVC_HIP_CHECK(hipStreamSynchronize(0));
+  }
+  return diffsvc_melpre(g, (const f16*)x16, OPD_LDX, OPD_NMEL, add, (f16*)hi, (f16*)lo, C, 1, M, s);
+}
+
+svc_status svc_op_diffsvc_skipsum(const void* g16, int NL, int rows_total, int row0, int rows, const float* w,
+                                  const float* bias, int bf16, void* s16, void* stream) {
+  SVC_REQUIRE(g16 && w && bias && s16 && NL >= 1 && NL <= 64, "op_diffsvc_skipsum: bad args");
+  SVC_REQUIRE(rows_total > 0 && row0 >= 0 && rows > 0 && (int64_t)row0 + rows <= rows_total,
+              "op_diffsvc_skipsum: rows [%d, %d + %d) of %d", row0, row0, rows, rows_total);
+  SVC_REQUIRE((int64_t)NL * rows_total * OPD_C * 2 < (1ll << 30), "op_diffsvc_skipsum: %d x %d rows", NL, rows_total);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = OPD_C;
+  PackFormat fmt(c, bf16);
+  OpPacks pk(c, s, 1);
+  std::vector<float> wh, bh;
+  int st;
+  if ((st = pack_from_device(w, (size_t)NL * C * C, bias, NL * C, wh, bh))) return st;
+  std::vector<const float*> ow(NL), ob(NL);
+  for (int l = 0; l < NL; ++l) {
+    ow[l] = wh.data() + (size_t)l * C * C;
+    ob[l] = bh.data() + (size_t)l * C;
+  }
+  if ((st = pack_skip_all(c, pk.g[0], ow.data(), ob.data(), C, NL))) return st;
+  // a sampler sub-batch: its rows of every layer's block, the layer stride that of the whole batch
+  return diffsvc_skipsum(pk.g[0], (const f16*)g16 + (size_t)row0 * C, (size_t)rows_total * C, NL, (f16*)s16, C, true,
+                         rows, s);
+}
+
+svc_status svc_op_diffsvc_head(const void* s16, int M, const float* wsp, const float* bsp, const float* wout,
+                               const float* bout, int bf16, float* eps, void* stream) {
+  SVC_REQUIRE(s16 && wsp && bsp && wout && bout && eps && M > 0, "op_diffsvc_head: bad args");
+  SVC_REQUIRE((int64_t)M * 3 * OPD_C * 2 < (1ll << 30), "op_diffsvc_head: %d rows", M);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = OPD_C;
+  PackFormat fmt(c, bf16);
+  OpPacks pk(c, s, 2);
+  std::vector<float> wh, bh, wh2, bh2;
+  int st;
+  if ((st = pack_from_device(wsp, (size_t)C * C, bsp, C, wh, bh))) return st;
+  if ((st = pack_from_device(wout, (size_t)OPD_NMEL * C, bout, OPD_NMEL, wh2, bh2))) return st;
+  if ((st = pack_conv1d_opt(c, pk.g[0], wh.data(), bh.data(), C, C, 1, C, 1, 0, 1, true))) return st;
+  if ((st = pack_conv1d_opt(c, pk.g[1], wh2.data(), bh2.data(), OPD_NMEL, C, 1, C, 1, 0, 1, true))) return st;
+  f16* u16;
+  if ((st = c->ws.plan([&](Arena& ws) { u16 = ws.get<f16>((size_t)M * 3 * C); }))) return st;
+  return diffsvc_head(pk.g[0], pk.g[1], (const f16*)s16, u16, eps, C, OPD_NMEL, true, 1, M, s);
+}
+
+svc_status svc_op_diffsvc_condproj(const float* cond, int M, int NL, const float* w, const float* bias, int bf16,
+                                   void* cp16, void* stream) {
+  SVC_REQUIRE(cond && w && bias && cp16 && M > 0 && NL >= 1 && NL <= 64, "op_diffsvc_condproj: bad args");
+  SVC_REQUIRE((int64_t)NL * M * 2 * OPD_C * 2 < (1ll << 30), "op_diffsvc_condproj: %d x %d rows", NL, M);
+  svc_ctx* c;
+  op_ws(&c);
+  TuningScope tuning_scope_(&c->tune);
+  hipStream_t s = (hipStream_t)stream;
+  const int C = OPD_C;
+  PackFormat fmt(c, bf16);
+  OpPacks pk(c, s, 1);
+  std::vector<float> wh, bh;
+  int st;
+  if ((st = pack_from_device(w, (size_t)NL * 2 * C * C, bias, NL * 2 * C, wh, bh))) return st;
+  std::vector<const float*> cw(NL), cb(NL);
+  for (int l = 0; l < NL; ++l) {
+    cw[l] = wh.data() + (size_t)l * 2 * C * C;
+    cb[l] = bh.data() + (size_t)l * 2 * C;
+  }
+  if ((st = pack_cond_all(c, pk.g[0], cw.data(), cb.data(), C, NL, C))) return st;
+  f16* cond16;
+  if ((st = c->ws.plan([&](Arena& ws) { cond16 = ws.get<f16>((size_t)M * 3 * C); }))) return st;
+  void* cpp;  // the projections in the gate GEMMs' paired order, as project_cond leaves them
+  if ((st = pk.alloc((size_t)NL * M * 2 * C * sizeof(f16), &cpp))) return st;
+  if ((st = diffsvc_condproj(pk.g[0], cond, cond16, (f16*)cpp, (size_t)M * 2 * C, C, bf16 != 0, 1, M, s))) return st;
+  SVC_HIP_CHECK(hipStreamSynchronize(s));
+  return permute_cp(cpp, cp16, (size_t)NL * M, C, false);
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------- GEMM microbenchmark

@@ -20,106 +20,147 @@ struct DenoiseBufs {
 };
 
 
+namespace svc {
+
+// Residual stream x in split-fp16 storage (x + dproj_l = hi + lo, ~22 significand bits in 4 bytes): the layer's GEMM
+// operand is its high half, so each residual update moves 10 instead of 12 bytes per element (an f32 residual stream
+// measured 1.1 % slower end to end at the same mel-L1, round 1; removed in round 3).
+int diffsvc_melpre(const PackedGemm& melpre, const f16* x16, int ldx16, int n_mel, const float* add, f16* hi, f16* lo,
+                   int C, int B, int T, hipStream_t s) {
+  if (tuning().res_proj && melpre.Wfrag && ldx16 <= 128) {
+    // weight-stationary store stream (res_proj.hip mel_proj), bit-identical to the tiled GEMM
+    prof_site("diffsvc.melpre");
+    return mel_proj(x16, ldx16, melpre.Wfrag, melpre.bias, add, hi, lo, B * T, melpre.bf16, s);
+  }
+  EpiArgs e = epi();
+  e.act = ACT_RELU;
+  e.lo16 = lo;
+  e.out16 = hi;
+  e.ld16 = C;
+  e.add16 = add;
+  return run_gemm(melpre, x16, ldx16, n_mel, B, T, T, e, s, "diffsvc.melpre");
+}
+
+int diffsvc_gate(const PackedGemm& dil, const f16* x16, const f16* cp, f16* y16, int C, int B, int T, const int* tv,
+                 hipStream_t s) {
+  EpiArgs g = epi();
+  g.kind = EPI_GATE;
+  g.cp = cp;
+  g.ld_cp = 2 * C;
+  g.y16 = y16;
+  g.ldy16 = C;
+  return run_gemm(dil, x16, C, C, B, T, T, g, s, "diffsvc.dilated", tv, 1);
+}
+
+int diffsvc_res_lanes() {
+  if (!tuning().res_proj) return -1;
+  return tuning().res_proj > 1 ? tuning().res_proj : (tuning().sampler_streams == 1 ? -2 : 0);
+}
+
+// x = (x + residual) / sqrt(2); next input x + diffusion_projection_{i+1}(step):
+// x_i = (hi + lo) - dproj_i (sub), and x_{i+1} + dproj_{i+1} (add) goes back split into hi / lo
+int diffsvc_residual(const PackedGemm& outres, const f16* g16, const float* sub, const float* add, f16* hi, f16* lo,
+                     int C, int B, int T, int lanes_cap, bool store_lo, hipStream_t s) {
+  if (lanes_cap != -1 && C == 384 && outres.Wfrag && outres.N == C && outres.K == C) {
+    // weight-stationary row stream (res_proj.hip), bit-identical to the tiled GEMM below
+    prof_site("diffsvc.outproj");
+    return res_proj(g16, outres.Wfrag, outres.bias, sub, add, 1.41421356237309515f, hi, lo, B * T, outres.bf16,
+                    lanes_cap, store_lo, s);
+  }
+  EpiArgs r = epi();
+  r.ld_acc = C;
+  r.acc_div = 1.41421356237309515f;
+  r.acc16_hi = hi;
+  r.acc16_lo = lo;
+  r.acc_sub = sub;
+  r.lo16 = lo;
+  r.out16 = hi;
+  r.ld16 = C;
+  r.add16 = add;
+  return run_gemm(outres, g16, C, C, B, T, T, r, s, "diffsvc.outproj");
+}
+
+// skip = sum_i skip_i (modules/diffsvc.py:311); x = skip / sqrt(len(layers)) (:315)
+int diffsvc_skipsum(const PackedGemm& skip_all, const f16* g16, size_t g_ls, int NL, f16* s16, int C, bool head_split,
+                    int rows, hipStream_t s) {
+  const int H3 = head_split ? 3 : 1;  // split-fp16 head operands are [hi | lo | hi] rows
+  EpiArgs e = epi();
+  e.scale_cols = C;
+  e.col_scale = 1.0f / sqrtf((float)NL);
+  e.out16 = s16;
+  e.ld16 = C * H3;
+  e.split16 = H3 == 3 ? C : 0;
+  PackedGemm sk = skip_all;  // K index l * C + k = "tap" l * Cp + k with Cp = C: same packed weights
+  sk.Cp = C;
+  sk.taps = NL;
+  sk.tap_mul = (int)(g_ls / C);
+  sk.tap_add = 0;
+  sk.istride = 1;
+  return run_gemm(sk, g16, C, C, 1, NL * sk.tap_mul, rows, e, s, "diffsvc.skipsum");
+}
+
+int diffsvc_head(const PackedGemm& skipproj, const PackedGemm& outproj, const f16* s16, f16* u16, float* eps, int C,
+                 int n_mel, bool head_split, int B, int T, hipStream_t s) {
+  const int H3 = head_split ? 3 : 1;
+  // relu(skip_projection) and output_projection in one launch: u never reaches HBM (diff_head.hip)
+  if (tuning().diff_head && H3 == 3 && C == 384 && skipproj.N == C && skipproj.Npad >= C && skipproj.K == 3 * C &&
+      skipproj.Kpad == 3 * C && outproj.K == 3 * C && outproj.Kpad == 3 * C && outproj.Npad >= 128 &&
+      outproj.N <= 128 && n_mel % 4 == 0)
+    return diff_head(s16, skipproj.W, skipproj.bias, C, 3 * C, outproj.W, outproj.bias, outproj.N, 3 * C, outproj.Npad,
+                     eps, n_mel, B * T, zero_page(), s, skipproj.bf16);
+  int st;
+  EpiArgs e = epi();
+  e.act = ACT_RELU;
+  e.out16 = u16;
+  e.ld16 = C * H3;
+  e.split16 = H3 == 3 ? C : 0;
+  if ((st = run_gemm(skipproj, s16, C * H3, C * H3, B, T, T, e, s, "diffsvc.skipproj"))) return st;
+  e = epi();
+  e.out32 = eps;
+  e.ld32 = n_mel;
+  return run_gemm(outproj, u16, C * H3, C * H3, B, T, T, e, s, "diffsvc.eps_out");
+}
+
+int diffsvc_condproj(const PackedGemm& cp_all, const float* cond, f16* cond16, f16* cp16, size_t cp_ls, int C,
+                     bool bf16, int B, int T, hipStream_t s) {
+  int st;
+  if ((st = f32_to_f16x3(cond, C, cond16, B * T, C, s, bf16))) return st;  // [hi | lo | hi] split-fp16 operand
+  // the projections of all layers as ONE GEMM over the packed weights (N = NL x 2C), each layer's 2C columns written
+  // to its layer-major cp block (EpiArgs col_block): 20 launches of 470 tiles (1.8 rounds of workgroups each) became
+  // one launch of 9 400 (round 5)
+  EpiArgs e = epi();
+  e.out16 = cp16;
+  e.ld16 = 2 * C;
+  e.col_block = 2 * C;
+  e.col_block_stride = (int64_t)cp_ls;
+  return run_gemm(cp_all, cond16, 3 * C, 3 * C, B, T, T, e, s, "diffsvc.condproj");
+}
+
+}  // namespace svc
+
 // tv (device, optional): ragged batches, utterance b has tv[b] valid frames; only the dilated convs look across frames
 // plms (optional): the PLMS update that consumes this eps, launched right after the head
 static int denoise(svc_ctx* c, const DenoiseBufs& bb, const f16* x16, int B, int T, int t, float* eps, hipStream_t s,
                    const int* tv, const PlmsArgs* plms = nullptr) {
   const int C = c->C, NL = c->n_layers, rows = B * T;
   const int ldx16 = (int)round_up(c->n_mel, 8);
-  const float* dp = c->dproj + (size_t)t * NL * C;
+  const float* dp = c->dproj + (size_t)t * NL * C;  // the step's diffusion projections, [NL][C]
   int st;
-  // Residual stream x in split-fp16 storage (x + dproj_l = y16 + lo16, ~22 significand bits in 4 bytes): the layer's
-  // GEMM operand y16 is its high half, so each residual update moves 10 instead of 12 bytes per element (an f32
-  // residual stream measured 1.1 % slower end to end at the same mel-L1, round 1; removed in round 3).
-  EpiArgs e = epi();
-  e.act = ACT_RELU;
-  e.lo16 = bb.lo16;
-  e.out16 = bb.y16;
-  e.ld16 = C;
-  e.add16 = dp;  // layer 0 diffusion projection
-  if (tuning().res_proj && c->melpre.Wfrag && ldx16 <= 128) {
-    // weight-stationary store stream (res_proj.hip mel_proj), bit-identical to the tiled GEMM
-    prof_site("diffsvc.melpre");
-    if ((st = mel_proj(x16, ldx16, c->melpre.Wfrag, c->melpre.bias, dp, bb.y16, bb.lo16, rows, c->melpre.bf16, s)))
-      return st;
-  } else if ((st = run_gemm(c->melpre, x16, ldx16, c->n_mel, B, T, T, e, s, "diffsvc.melpre"))) {
-    return st;
-  }
+  if ((st = diffsvc_melpre(c->melpre, x16, ldx16, c->n_mel, dp, bb.y16, bb.lo16, C, B, T, s))) return st;
   // the split residual stream's high half, updated in place (y16) by gate + res_proj
   f16* hi = bb.y16;
   for (int i = 0; i < NL; ++i) {
-    EpiArgs g = epi();
-    g.kind = EPI_GATE;
-    g.cp = bb.cp16 + (size_t)i * bb.cp_ls;
-    g.ld_cp = 2 * C;
-    g.y16 = bb.g16 + (size_t)i * bb.g_ls;
-    g.ldy16 = C;
-    if ((st = run_gemm(c->dil[i], hi, C, C, B, T, T, g, s, "diffsvc.dilated", tv, 1))) return st;
+    f16* g16 = bb.g16 + (size_t)i * bb.g_ls;
+    if ((st = diffsvc_gate(c->dil[i], hi, bb.cp16 + (size_t)i * bb.cp_ls, g16, C, B, T, tv, s))) return st;
     if (i + 1 == NL) break;  // the last layer's residual output is unused (only skips feed the head)
-    // x = (x + residual) / sqrt(2); next input x + diffusion_projection_{i+1}(step):
-    // x_i = (y16 + lo16) - dproj_i, and x_{i+1} + dproj_{i+1} goes back split into y16 / lo16
-    if (tuning().res_proj && C == 384 && c->outres[i].Wfrag && c->outres[i].N == C && c->outres[i].K == C) {
-      // weight-stationary row stream (res_proj.hip), bit-identical to the tiled GEMM below
-      prof_site("diffsvc.outproj");
-      if ((st = res_proj(bb.g16 + (size_t)i * bb.g_ls, c->outres[i].Wfrag, c->outres[i].bias,
-                         dp + (size_t)i * C, dp + (size_t)(i + 1) * C, 1.41421356237309515f, hi, bb.lo16, rows,
-                         c->outres[i].bf16,
-                         tuning().res_proj > 1 ? tuning().res_proj : (tuning().sampler_streams == 1 ? -2 : 0),
-                         i + 2 < NL /* the last residual layer's low half is never read: layer NL - 1 has no update */,
-                         s)))
-        return st;
-      continue;
-    }
-    EpiArgs r = epi();
-    r.ld_acc = C;
-    r.acc_div = 1.41421356237309515f;
-    r.acc16_hi = hi;
-    r.acc16_lo = bb.lo16;
-    r.acc_sub = dp + (size_t)i * C;
-    r.lo16 = bb.lo16;
-    r.out16 = hi;
-    r.ld16 = C;
-    r.add16 = dp + (size_t)(i + 1) * C;
-    if ((st = run_gemm(c->outres[i], bb.g16 + (size_t)i * bb.g_ls, C, C, B, T, T, r, s, "diffsvc.outproj"))) return st;
-  }
-  // skip = sum_i skip_i (modules/diffsvc.py:311); x = skip / sqrt(len(layers)) (:315)
-  const int H3 = c->head_split ? 3 : 1;  // split-fp16 head operands are [hi | lo | hi] rows
-  e = epi();
-  e.scale_cols = C;
-  e.col_scale = 1.0f / sqrtf((float)NL);
-  e.out16 = bb.s16;
-  e.ld16 = C * H3;
-  e.split16 = H3 == 3 ? C : 0;
-  {
-    PackedGemm sk = c->skip_all;  // K index l * C + k = "tap" l * Cp + k with Cp = C: same packed weights
-    sk.Cp = C;
-    sk.taps = NL;
-    sk.tap_mul = (int)(bb.g_ls / C);
-    sk.tap_add = 0;
-    sk.istride = 1;
-    const int rows_sub = B * T;
-    if ((st = run_gemm(sk, bb.g16, C, C, 1, NL * sk.tap_mul, rows_sub, e, s, "diffsvc.skipsum"))) return st;
-  }
-  // relu(skip_projection) and output_projection in one launch: u never reaches HBM (diff_head.hip)
-  if (tuning().diff_head && H3 == 3 && C == 384 && c->skipproj.N == C && c->skipproj.Npad >= C &&
-      c->skipproj.K == 3 * C && c->skipproj.Kpad == 3 * C && c->outproj.K == 3 * C && c->outproj.Kpad == 3 * C &&
-      c->outproj.Npad >= 128 && c->outproj.N <= 128 && c->n_mel % 4 == 0) {
-    if ((st = diff_head(bb.s16, c->skipproj.W, c->skipproj.bias, C, 3 * C, c->outproj.W, c->outproj.bias,
-                        c->outproj.N, 3 * C, c->outproj.Npad, eps, c->n_mel, (int)rows, zero_page(), s,
-                        c->skipproj.bf16)))
+    if ((st = diffsvc_residual(c->outres[i], g16, dp + (size_t)i * C, dp + (size_t)(i + 1) * C, hi, bb.lo16, C, B, T,
+                               diffsvc_res_lanes(),
+                               i + 2 < NL /* the last residual layer's low half is never read: layer NL - 1 has no update */,
+                               s)))
       return st;
-    return plms ? plms_update(*plms, rows, c->n_mel, s) : SVC_OK;
   }
-  e = epi();
-  e.act = ACT_RELU;
-  e.out16 = bb.u16;
-  e.ld16 = C * H3;
-  e.split16 = H3 == 3 ? C : 0;
-  if ((st = run_gemm(c->skipproj, bb.s16, C * H3, C * H3, B, T, T, e, s, "diffsvc.skipproj"))) return st;
-  e = epi();
-  e.out32 = eps;
-  e.ld32 = c->n_mel;
-  if ((st = run_gemm(c->outproj, bb.u16, C * H3, C * H3, B, T, T, e, s, "diffsvc.eps_out"))) return st;
+  if ((st = diffsvc_skipsum(c->skip_all, bb.g16, bb.g_ls, NL, bb.s16, C, c->head_split, rows, s))) return st;
+  if ((st = diffsvc_head(c->skipproj, c->outproj, bb.s16, bb.u16, eps, C, c->n_mel, c->head_split, B, T, s))) return st;
   return plms ? plms_update(*plms, rows, c->n_mel, s) : SVC_OK;
 }
 
@@ -138,19 +179,7 @@ static void layout_denoise(svc_ctx* c, Arena& ws, int B, int T, DenoiseBufs& bb)
 }
 
 static int project_cond(svc_ctx* c, const float* cond, int B, int T, const DenoiseBufs& bb, hipStream_t s) {
-  const int rows = B * T, C = c->C;
-  int st;
-  if ((st = f32_to_f16x3(cond, C, bb.cond16, rows, C, s, c->bf16))) return st;  // [hi | lo | hi] split-fp16 operand
-  // the projections of all layers as ONE GEMM over the packed weights (N = NL x 2C), each layer's 2C columns written
-  // to its layer-major cp block (EpiArgs col_block): 20 launches of 470 tiles (1.8 rounds of workgroups each) became
-  // one launch of 9 400 (round 5)
-  EpiArgs e = epi();
-  e.out16 = bb.cp16;
-  e.ld16 = 2 * C;
-  e.col_block = 2 * C;
-  e.col_block_stride = (int64_t)bb.cp_ls;
-  if ((st = run_gemm(c->cp_all, bb.cond16, 3 * C, 3 * C, B, T, T, e, s, "diffsvc.condproj"))) return st;
-  return SVC_OK;
+  return diffsvc_condproj(c->cp_all, cond, bb.cond16, bb.cp16, bb.cp_ls, c->C, c->bf16, B, T, s);
 }
 
 namespace svc {
