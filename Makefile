@@ -27,6 +27,13 @@ build/res_proj.o build/gate_ws.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_D
 	@python3 tools/check_kernel_resources.py build/$*.res $(if $(filter res_proj,$*),'res_proj_kernelILb.ELi.ELb.ELi0E' 104,gate_ws 256) || { rm -f $@; exit 1; }
 	@$(if $(filter res_proj,$*),python3 tools/check_kernel_resources.py build/$*.res 'res_proj_(ws_)?kernel' 256 || { rm -f $@; exit 1; })
 
+# the direct DFT keeps 2 bins x 8 frames of f64 sums per thread (64 registers) and one workgroup of 160 KiB of LDS per
+# CU: a spill would put its inner loop on scratch
+build/mel_keyshift.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include/svc_hip.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
+	@python3 tools/check_kernel_resources.py build/$*.res mel_keyshift_kernel 256 || { rm -f $@; exit 1; }
+
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -o $@
 

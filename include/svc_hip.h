@@ -8,7 +8,10 @@
  *   svc_f0_ac           <- utils/f0.py:120-161 get_f0_features_using_parselmouth (Praat to_pitch_ac + pad)
  *   svc_pitch_shift     <- utils/acoustic_feature_extraction.py:48-52 pitch_shift
  *   svc_pitch_shift_ex  <- the same with a target median (and an optional key scale) per utterance
+ *   svc_pitch_factor    <- the factor svc_pitch_shift / svc_pitch_shift_ex multiply by, stored instead of applied
  *   svc_f0_voiced_median <- utils/acoustic_feature_extraction.py:21-30 get_target_f0_median (a singer's pooled contours)
+ *   svc_mel_keyshift    <- Diff-SVC's key-shifted mel (utils/mel.py:43-117 get_mel(keyshift=), with the hop held): the
+ *                          start mel of shallow diffusion moved by the pitch factor
  *   svc_whisper_encode  <- utils/whisper.py:13-28 whisper_encoder (log_mel_spectrogram + AudioEncoder)
  *   svc_map_content     <- utils/whisper.py:31-81 get_mapped_whisper_features
  *   svc_whisper_content_ragged <- utils/whisper.py:13-81, both of the above for a ragged batch: every 30 s window that
@@ -139,6 +142,36 @@ svc_status svc_pitch_shift(svc_ctx* ctx, double* f0, int B, int T, double target
    tables are staged through the feature stages' ring, like the ragged-batch lengths. */
 svc_status svc_pitch_shift_ex(svc_ctx* ctx, double* f0, int B, int T, const double* target_median,
                               const double* scale, void* stream);
+
+/* A4's factor without the shift: factor[b] = target_median[b] / median(voiced f0[b, :]), then * scale[b] where scale is
+   given: svc_pitch_shift_ex's select and operations in its order (with scale NULL and equal targets svc_pitch_shift's),
+   so f0 * factor in f64 is bit for bit what those calls write. f0 [B*T] f64 is only read; factor: DEVICE f64 [B],
+   stream-ordered, NaN for a row with no voiced frame. target_median, scale: HOST f64 [B] (scale NULL = none), finite
+   and > 0 (checked before any device call, SVC_ERR_INVALID otherwise), staged like svc_pitch_shift_ex's. One
+   workgroup per row. */
+svc_status svc_pitch_factor(svc_ctx* ctx, const double* f0, int B, int T, const double* target_median,
+                            const double* scale, double* factor, void* stream);
+
+/* The key-shifted log-mel: svc_mel_energy's mel of a voice whose pitch is moved by factor[b], from the unmoved audio.
+   wav24k [B][n_samples] f32, factor DEVICE f64 [B] (svc_pitch_factor's) -> mel [B*T][n_mels] f32; T, utt_samples and
+   each utterance's T_b as in svc_mel_energy; no energy. Utterance b, with n = n_fft:
+     n_new   = rint(n * factor[b]) (f64 product, half to even), clamped to [n / 2, 2 n]; a factor that is not finite or
+               <= 0 is taken as 1 (n_new = n). info (DEVICE int32 [B] or NULL): bit 0 such a factor, bit 1 the clamp
+               acted, else 0. All on the device: nothing is read back, and a bad factor does not stop the batch.
+     window  w[j] = (float)(0.5 - 0.5 cos(2 pi j / n_new)) (f64, periodic Hann), the multiply x * w[j] in f32.
+     frame t reads samples t * hop + j - (n_new - hop) / 2, j < n_new: the hop is held, so the frame count is the
+               unshifted one. One reflection at either end against the utterance's own length; samples at or past it
+               are never read.
+     X[k]    = sum_j xw[j] e^(-2 pi i k j / n_new), k = 0 .. min(n / 2, n_new / 2), in f64 (a direct DFT with exact
+               integer phases); |X| = sqrtf(re^2 + im^2 + 1e-9f) on the f32 casts, then * (float)n / (float)n_new (two f32
+               operations, in that order) where n_new != n. Bins k > n_new / 2 (a downward shift) are exactly 0.
+     mel     = the context's slaney filterbank and logf(fmaxf(., 1e-5f)), svc_mel_energy's f32 sequence.
+   Rows t >= T_b are zeros. SVC_ERR_INVALID before any device call: a null pointer, B < 1, n_fft other than 512 or 1024
+   (or hop > n_fft / 2), a context without a mel filterbank, or an utterance of (2 n - hop + 1) / 2 samples or fewer
+   (the widest window's reflection must stay inside the clip). Uses the feature stages' length ring and no workspace:
+   may run beside the content encoder like svc_mel_energy. */
+svc_status svc_mel_keyshift(svc_ctx* ctx, const float* wav24k, int B, int64_t n_samples, const int64_t* utt_samples,
+                            const double* factor, float* mel, int32_t* info, void* stream);
 
 /* A4, the target side: np.median of every f0[b, t] != 0 with t < frames[b] (frames: host int32 [B], NULL = all T),
    pooled over the batch: utils/acoustic_feature_extraction.py:21-30. median: device f64 [1] (NaN where nothing is

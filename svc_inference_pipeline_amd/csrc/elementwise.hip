@@ -815,6 +815,26 @@ int pitch_shift_ex(double* f0, int B, int T, const double* target, const double*
   return SVC_OK;
 }
 
+// svc_pitch_factor: the factor pitch_shift_ex_kernel forms (the same select and operations in the same order; with
+// scale NULL and equal targets pitch_shift_kernel's), stored instead of applied: f0 is only read
+__global__ __launch_bounds__(256) void pitch_factor_kernel(const double* __restrict__ f0, int T,
+                                                           const double* __restrict__ target,
+                                                           const double* __restrict__ scale,
+                                                           double* __restrict__ out) {
+  __shared__ int red[4];
+  const double med = voiced_median(f0 + (int64_t)blockIdx.x * T, T, red);
+  double factor = target[blockIdx.x] / med;
+  if (scale) factor = factor * scale[blockIdx.x];
+  if (threadIdx.x == 0) out[blockIdx.x] = factor;
+}
+
+int pitch_factor(const double* f0, int B, int T, const double* target, const double* scale, double* factor,
+                 hipStream_t s) {
+  hipLaunchKernelGGL(pitch_factor_kernel, dim3(B), dim3(256), 0, s, f0, T, target, scale, factor);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
 // svc_f0_voiced_median: the select of median.h in its measured counting form, its histograms and state in the
 // feature stages' workspace
 int f0_voiced_median(const double* f0, int B, int T, const int* frames_dev, double* median, long long* voiced,

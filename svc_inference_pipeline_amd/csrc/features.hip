@@ -20,13 +20,6 @@
 
 namespace svc {
 
-__device__ __forceinline__ float spec_value(double re, double im, int mode) {
-  const float r = (float)re, i = (float)im;
-  if (mode == 0) return sqrtf(r * r + i * i + 1e-9f);
-  const float m = sqrtf(r * r + i * i);
-  return m * m;
-}
-
 // radix plans: N = n/2 complex points, TPF threads per frame (one per butterfly of the widest stage), FR frames per
 // workgroup
 template <int N>

@@ -61,6 +61,9 @@ int diff_head(const f16* s16, const f16* Wsp, const float* bsp, int Nsp, int Ksp
 int pitch_shift(double* f0, int B, int T, double target, hipStream_t s);
 // target, scale: device f64 [B] (scale NULL: none)
 int pitch_shift_ex(double* f0, int B, int T, const double* target, const double* scale, hipStream_t s);
+// the factor pitch_shift_ex multiplies row b by, f0 only read. target, scale as above; factor: device f64 [B]
+int pitch_factor(const double* f0, int B, int T, const double* target, const double* scale, double* factor,
+                 hipStream_t s);
 // the pooled voiced median (median.h). frames_dev: device int32 [B] or NULL; median: device f64 [1]; voiced: device
 // int64 [1] or NULL
 int f0_voiced_median(const double* f0, int B, int T, const int* frames_dev, double* median, long long* voiced,

@@ -79,6 +79,62 @@ svc_status svc_mel_energy(svc_ctx* c, const float* wav, int B, int64_t n, const 
   return SVC_OK;
 }
 
+// ---------------------------------------------------------------------------- key-shifted mel
+svc_status svc_mel_keyshift(svc_ctx* c, const float* wav, int B, int64_t n, const int64_t* n_samples,
+                            const double* factor, float* mel, int32_t* info, void* stream) {
+  // every argument check comes before the first HIP call
+  TuningScope tuning_scope_(c ? &c->tune : nullptr);
+  SVC_REQUIRE(c, "null context");
+  SVC_REQUIRE(wav && factor && mel, "mel_keyshift: null %s", !wav ? "wav" : !factor ? "factor" : "mel");
+  SVC_REQUIRE(B >= 1, "mel_keyshift: B=%d", B);
+  if (!c->finalized) {
+    set_error("context not finalized");
+    return SVC_ERR_STATE;
+  }
+  SVC_REQUIRE(c->n_fft == 512 || c->n_fft == 1024, "mel_keyshift: n_fft %d (512 or 1024)", c->n_fft);
+  SVC_REQUIRE(c->hop > 0 && c->hop <= c->n_fft / 2, "mel_keyshift: hop %d with n_fft %d", c->hop, c->n_fft);
+  SVC_REQUIRE(c->fb24 && c->band24 && c->fb24_len > 0, "mel_keyshift: the context has no mel filterbank");
+  // the widest window (2 n_fft) reflects (2 n_fft - hop) / 2 samples at the start and up to one more at the end: each
+  // utterance must hold them
+  const int64_t min_len = (2 * (int64_t)c->n_fft - c->hop + 1) / 2;
+  const int64_t T64 = mel_frames_of(c, n);
+  SVC_REQUIRE(n > min_len && T64 > 0 && T64 < (1 << 30), "mel_keyshift: n=%lld (more than %lld samples)", (long long)n,
+              (long long)min_len);
+  if (n_samples)
+    for (int b = 0; b < B; ++b)
+      SVC_REQUIRE(n_samples[b] > min_len && n_samples[b] <= n,
+                  "mel_keyshift: utterance %d: %lld samples (more than %lld, batch length %lld)", b,
+                  (long long)n_samples[b], (long long)min_len, (long long)n);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  const int T = (int)T64;
+  const int64_t* nb_dev;
+  const int* Tb_dev;
+  std::vector<int> Tb_host;
+  RingRetire retire_(c->lens_feat, s);
+  int st = stage_samples(c, c->lens_feat, n_samples, B, n, s, &nb_dev, &Tb_dev, &Tb_host);
+  if (st) return st;
+  KeyshiftArgs a{};
+  a.wav = wav;
+  a.wav_stride = n;
+  a.n_samples = n;
+  a.n_fft = c->n_fft;
+  a.hop = c->hop;
+  a.n_frames = T;
+  a.factor = factor;
+  a.fb = c->fb24;
+  a.band = c->band24;
+  a.fb_len = c->fb24_len;
+  a.n_mels = c->n_mels;
+  a.out = mel;
+  a.info = info;
+  a.nb = nb_dev;
+  a.Tb = Tb_dev;
+  if ((st = mel_keyshift(a, B, s))) return st;
+  if (Tb_dev && (st = zero_tail_rows(mel, B, T, c->n_mels, Tb_dev, s))) return st;
+  return SVC_OK;
+}
+
 // ---------------------------------------------------------------------------- F0
 svc_status svc_f0_ac(svc_ctx* c, const float* wav, int B, int64_t n, const int64_t* n_samples, int T, double* f0,
                      void* stream) {
@@ -175,6 +231,32 @@ svc_status svc_pitch_shift_ex(svc_ctx* c, double* f0, int B, int T, const double
   if (int st = c->lens_feat.put(tab.data(), tab.size() * sizeof(double), s, &dev)) return st;
   const double* td = reinterpret_cast<const double*>(dev);
   return pitch_shift_ex(f0, B, T, td, scale ? td + B : nullptr, s);
+}
+
+svc_status svc_pitch_factor(svc_ctx* c, const double* f0, int B, int T, const double* target_median,
+                            const double* scale, double* factor, void* stream) {
+  SVC_REQUIRE(c, "pitch_factor: null context");
+  SVC_REQUIRE(f0 && target_median && factor && B > 0 && T > 0, "pitch_factor: bad args (B=%d T=%d)", B, T);
+  // svc_pitch_shift_ex's staged table: f64 target[B], then f64 scale[B] where given; checked before any HIP call
+  const int cols = scale ? 2 : 1;
+  std::vector<double> tab((size_t)B * cols);
+  for (int b = 0; b < B; ++b) {
+    SVC_REQUIRE(std::isfinite(target_median[b]) && target_median[b] > 0.0,
+                "pitch_factor: utterance %d: target median %g (must be finite and positive)", b, target_median[b]);
+    tab[b] = target_median[b];
+    if (scale) {
+      SVC_REQUIRE(std::isfinite(scale[b]) && scale[b] > 0.0,
+                  "pitch_factor: utterance %d: scale %g (must be finite and positive)", b, scale[b]);
+      tab[(size_t)B + b] = scale[b];
+    }
+  }
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_feat, s);
+  void* dev = nullptr;
+  if (int st = c->lens_feat.put(tab.data(), tab.size() * sizeof(double), s, &dev)) return st;
+  const double* td = reinterpret_cast<const double*>(dev);
+  return pitch_factor(f0, B, T, td, scale ? td + B : nullptr, factor, s);
 }
 
 svc_status svc_f0_voiced_median(svc_ctx* c, const double* f0, int B, int T, const int32_t* frames, double* median,

@@ -28,7 +28,7 @@ from dataclasses import dataclass
 
 import torch
 
-from .runtime import SVCEngine, check_k_step, mel_frames
+from .runtime import SVCEngine, check_k_step, check_k_step_mel, mel_frames
 
 WHISPER_WINDOW = 478720       # 16 kHz samples per long-input window (29.92 s)
 WINDOW_MEL_FRAMES = 2805      # = 1496 encoder frames * 15 / 8
@@ -110,21 +110,26 @@ class SVCPipeline:
         target_f0_median for a singer that is not enrolled), then up by key_shift semitones (a scalar or one per clip;
         the factor 2 ** (k / 12) is computed here in f64). With an empty table and no shift this is the scalar call
         svc_pitch_shift as before, and `singers` (which may be a device tensor) is not looked at."""
+        return self.engine.pitch_shift(f0, *self.shift_targets(f0.shape[0], singers, key_shift))
+
+    def shift_targets(self, B, singers, key_shift=0.0):
+        """The arguments after f0 with which shift_f0 calls engine.pitch_shift for a batch of B (engine.pitch_factor
+        takes the same): none, the scalar route, with an empty singer table and no key shift; else (targets, scale), one
+        target per clip and, with a key shift, one scale per clip (else None)."""
         e = self.engine
-        B = f0.shape[0]
         table = getattr(e, "singer_f0", None)
         ks = key_shift.tolist() if hasattr(key_shift, "tolist") else key_shift
         ks = [float(k) for k in ks] if isinstance(ks, (list, tuple)) else [float(ks)] * B
         if len(ks) != B:
             raise ValueError(f"{len(ks)} key shifts for a batch of {B}")
         if not table and not any(ks):
-            return e.pitch_shift(f0)
+            return ()
         ids = singers.reshape(-1).tolist() if hasattr(singers, "tolist") else list(singers)
         if len(ids) != B:
             raise ValueError(f"{len(ids)} singers for a batch of {B}")
         targets = [table.get(s, e.target_f0_median) if table else e.target_f0_median for s in ids]
         scale = [2.0 ** (k / 12.0) for k in ks] if any(ks) else None
-        return e.pitch_shift(f0, targets, scale)
+        return targets, scale
 
     def enroll(self, singer, sources=None, wavs24=None, max_batch=16):
         """Measure a singer's voiced F0 median from that singer's own recordings and record it as the singer's pitch
@@ -211,25 +216,29 @@ class SVCPipeline:
         return self._side
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
-                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None):
+                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
         Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
         save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`.
         key_shift: semitones on top of the shift to the singer's median, a scalar or one per clip (shift_f0).
         k_step (shallow diffusion; None: the full schedule from noise, the call as before): the sampler starts from the
         source's own mel noised to level k_step - 1 and denoises from there (SVCEngine.diffsvc_sample(k_step, mel_src));
-        x_T is not used then."""
+        x_T is not used then.
+        k_step_mel (with k_step): "source" (default) starts from the clip's own mel; "shifted" from its key-shifted mel
+        (SVCEngine.mel_keyshift by the factor shift_f0 applies, SVCEngine.pitch_factor), so the start state's harmonics
+        sit at the pitch the conditioner asks for. ConvertResult.mel stays the unshifted source mel."""
         k_step = self._check_k_step(k_step)
+        check_k_step_mel(k_step_mel, k_step)
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
-                                 wav16_float, pcm16, key_shift, k_step)
+                                 wav16_float, pcm16, key_shift, k_step, k_step_mel == "shifted")
 
     def _check_k_step(self, k_step):
         """k_step validated against the engine's schedule (ValueError before any device work); None stays None."""
         return None if k_step is None else check_k_step(k_step, getattr(self.engine, "cfg", None))
 
     def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
-                 pcm16=False, key_shift=0.0, k_step=None):
+                 pcm16=False, key_shift=0.0, k_step=None, shifted=False):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -242,11 +251,16 @@ class SVCPipeline:
             mel, energy = e.mel_energy(wav24)
             # a caller-supplied f0 is shifted on a copy (svc_pitch_shift works in place)
             f0 = self.extract_f0(wav24, T) if f0 is None else f0.to(torch.float64).contiguous().clone()
+            mel_src, factor = mel, None
+            if shifted:  # the factor shift_f0 is about to apply, from the unshifted f0
+                factor = e.pitch_factor(f0, *self.shift_targets(f0.shape[0], singer, key_shift))
             self.shift_f0(f0, singer, key_shift)
+            if shifted:
+                mel_src, info = e.mel_keyshift(wav24, factor)
         assert mel.shape[1] == T
         content = self.content(wav16, T, wav16_float)
         main.wait_stream(side)
-        for t in (mel, energy, f0):
+        for t in (mel, energy, f0) + ((mel_src, factor, info) if shifted else ()):
             t.record_stream(main)
         cond = e.condition(content, f0, energy, singer)
         if utt_ids is None and (x_T is None or k_step is not None):
@@ -254,14 +268,14 @@ class SVCPipeline:
         if k_step is None:
             x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, x_T=x_T, noise=noise,
                                   seed=seed, utt_ids=utt_ids)
-        else:  # mel was computed on the side stream: joined and recorded for this one above
+        else:  # the start mel was computed on the side stream: joined and recorded for this one above
             x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, noise=noise, seed=seed,
-                                  utt_ids=utt_ids, k_step=k_step, mel_src=mel)
+                                  utt_ids=utt_ids, k_step=k_step, mel_src=mel_src)
         wav = e.bigvgan(x0)
         return ConvertResult(wav=wav, mel=mel, f0=f0, x0=x0, pcm=e.pcm16(wav) if pcm16 else None)
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None):
+                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -273,9 +287,11 @@ class SVCPipeline:
         pcm16=True: each waveform comes back as save_audio's samples instead, int16 [T_i*hop + 2*(fs//20)]
         (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak).
         key_shift: semitones, a scalar or one per utterance (shift_f0).
-        k_step: shallow diffusion for the whole batch, as in convert()."""
+        k_step, k_step_mel: shallow diffusion for the whole batch and its start mel, as in convert()."""
         k_step = self._check_k_step(k_step)
         shallow = {} if k_step is None else dict(k_step=k_step)
+        if check_k_step_mel(k_step_mel, k_step) != "source":
+            shallow["k_step_mel"] = k_step_mel
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
             raise ValueError("convert_many: wavs24, wavs16, singers (and wavs16_float) must have one entry per utterance")
@@ -369,20 +385,22 @@ class SVCPipeline:
         return out
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None):
+                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
         [T_b * hop + 2 * (fs // 20)] (svc_pcm16 with the same lengths). Each clip's F0 moves onto its own singer's
         median (shift_f0), then up by key_shift semitones (a scalar or one per clip). k_step: shallow diffusion, as in
-        convert(): each clip starts from its own mel, noised with its own utterance id's draw."""
+        convert(): each clip starts from its own mel (k_step_mel="shifted": its own key-shifted mel, by its own factor),
+        noised with its own utterance id's draw."""
         k_step = self._check_k_step(k_step)
+        check_k_step_mel(k_step_mel, k_step)
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                                        pcm16, key_shift, k_step)
+                                        pcm16, key_shift, k_step, k_step_mel == "shifted")
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
-                      float16k=None, key_shift=0.0, k_step=None):
+                      float16k=None, key_shift=0.0, k_step=None, k_step_mel="source"):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
@@ -391,6 +409,7 @@ class SVCPipeline:
         Without a HuBERT type and with None or False, load_batch is called without the keyword."""
         from . import audio as A
         k_step = self._check_k_step(k_step)
+        check_k_step_mel(k_step_mel, k_step)
         if wants_float16k(self.engine.cfg) if float16k is None else float16k:
             wavs24, wavs16, wavs16_float = A.load_batch(sources, self.engine.cfg.fs, self.engine, float16k=True)
         else:
@@ -398,10 +417,11 @@ class SVCPipeline:
             wavs16_float = None
         return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float, fast_inference=fast_inference,
                                    speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift,
-                                   **({} if k_step is None else dict(k_step=k_step)))
+                                   **({} if k_step is None else dict(k_step=k_step)),
+                                   **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)))
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                        pcm16=False, key_shift=0.0, k_step=None):
+                        pcm16=False, key_shift=0.0, k_step=None, shifted=False):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -415,16 +435,21 @@ class SVCPipeline:
         with torch.cuda.stream(side):
             mel, energy = e.mel_energy(w24, n_samples=n24)
             f0 = self.extract_f0(w24, T, n_samples=n24, T_b=T_b)
+            mel_src, factor = mel, None
+            if shifted:  # as in _convert
+                factor = e.pitch_factor(f0, *self.shift_targets(n, [int(s) for s in singers], key_shift))
             self.shift_f0(f0, [int(s) for s in singers], key_shift)
+            if shifted:
+                mel_src, info = e.mel_keyshift(w24, factor, n_samples=n24)
         content = self.ragged_content(list(wavs16), T_b, T, wavs16_float)
         main.wait_stream(side)
-        for t in (mel, energy, f0):
+        for t in (mel, energy, f0) + ((mel_src, factor, info) if shifted else ()):
             if t.is_cuda:
                 t.record_stream(main)
         sing = torch.tensor([int(s) for s in singers], device=dev, dtype=torch.int32)
         cond = e.condition(content, f0, energy, sing)
         uid = torch.tensor(ids, device=dev, dtype=torch.int32)
-        shallow = {} if k_step is None else dict(k_step=k_step, mel_src=mel)  # mel: joined and recorded above
+        shallow = {} if k_step is None else dict(k_step=k_step, mel_src=mel_src)  # joined and recorded above
         x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=uid, frames=T_b,
                               **shallow)
         wav = e.bigvgan(x0, frames=T_b)

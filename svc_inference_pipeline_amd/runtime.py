@@ -69,6 +69,19 @@ def check_k_step(k_step, cfg=None):
     return int(k_step)
 
 
+K_STEP_MELS = ("source", "shifted")
+
+
+def check_k_step_mel(k_step_mel, k_step):
+    """Shallow diffusion's start mel: "source" (the clip's own mel) or "shifted" (its key-shifted mel, mel_keyshift by
+    the F0 factor), which needs a k_step; else ValueError before any device work."""
+    if k_step_mel not in K_STEP_MELS:
+        raise ValueError(f"k_step_mel {k_step_mel!r}: 'source' or 'shifted'")
+    if k_step_mel == "shifted" and k_step is None:
+        raise ValueError("k_step_mel='shifted' needs k_step (shallow diffusion)")
+    return k_step_mel
+
+
 def check_supported(cfg):
     """Reject configurations the native path does not implement, before any device work (raise ValueError)."""
     merge = getattr(cfg.mapper, "merge_mode", "add")
@@ -282,6 +295,33 @@ class SVCEngine:
         _lib.call("svc_pitch_shift_ex", self._ctx, _ptr(f0), B, T, _host_table(tm, B, "target_median"),
                   None if scale is None else _host_table(scale, B, "scale"), _stream())
         return f0
+
+    def pitch_factor(self, f0, target_median=None, scale=None):
+        """The factor pitch_shift(f0, target_median, scale) multiplies each row by, without applying it: f0 f64 [B, T]
+        is only read -> f64 [B] on the device, stream-ordered (NaN for a row with no voiced frame). The arguments are
+        pitch_shift's; f0 * factor is bit for bit what it writes (svc_pitch_factor)."""
+        B, T = f0.shape
+        tm = self.target_f0_median if target_median is None else target_median
+        factor = torch.empty(B, device=f0.device, dtype=torch.float64)
+        _lib.call("svc_pitch_factor", self._ctx, _ptr(f0), B, T, _host_table(tm, B, "target_median"),
+                  None if scale is None else _host_table(scale, B, "scale"), _ptr(factor), _stream())
+        return factor
+
+    def mel_keyshift(self, wav24, factor, n_samples=None):
+        """wav24 f32 [B, N], factor f64 [B] on the device (pitch_factor's) -> (the key-shifted log-mel f32
+        [B, T, n_mels], info int32 [B]): mel_energy's mel of the same voice with its pitch moved by factor[b], from a
+        window and transform of rint(n_fft * factor[b]) samples at the same hop (svc_mel_keyshift; Diff-SVC's start mel
+        for shallow diffusion). info[b]: 1 the factor was not finite or <= 0 and was taken as 1, 2 the length was
+        clamped to [n_fft / 2, 2 n_fft], else 0; nothing is read back. n_samples as in mel_energy."""
+        B, N = wav24.shape
+        T = mel_frames(N, self.cfg.n_fft, self.cfg.hop_length)
+        if factor is not None and (factor.dtype != torch.float64 or factor.numel() != B):
+            raise ValueError(f"mel_keyshift: factor must be f64 [{B}]")
+        mel = torch.empty(B, max(T, 0), self.cfg.n_mels, device=wav24.device, dtype=torch.float32)
+        info = torch.empty(B, device=wav24.device, dtype=torch.int32)
+        _lib.call("svc_mel_keyshift", self._ctx, _ptr(wav24), B, N, _host_lengths(n_samples, B, ctypes.c_int64),
+                  _ptr(factor), _ptr(mel), _ptr(info), _stream())
+        return mel, info
 
     def f0_voiced_median(self, f0, frames=None):
         """np.median of the voiced (nonzero) cells of f0 f64 [B, T] (or [T]) with t < frames[b] (host ints [B]; None:

@@ -14,7 +14,8 @@ it (so padding stays bounded: the kernels skip the padded tail, but its rows sti
 `max_batch`, waits at most `max_wait_s` for a batch to fill, and runs SVCPipeline.convert_ragged on it. Each request
 carries an utterance id (given, or a running counter) that keys its device noise, so its waveform is bit-identical to
 converting that clip alone with the same id, whatever it was batched with (tests/test_gpu_ragged.py). A request may ask
-for shallow diffusion (`k_step`); a batch is formed only from requests with the same `k_step`.
+for shallow diffusion (`k_step`, and `k_step_mel` for its start mel); a batch is formed only from requests with the same
+`k_step` and `k_step_mel`.
 
 Streams: submit() records an event on the caller's current stream, and the worker's stream waits for it before it
 reads the request's tensors, so inputs produced by kernels still in flight on the caller's stream are safe to
@@ -37,7 +38,7 @@ import torch
 from . import _lib
 from . import audio as A
 from .pipeline import SVCPipeline, wants_float16k
-from .runtime import check_k_step, mel_frames
+from .runtime import check_k_step, check_k_step_mel, mel_frames
 
 
 @dataclass
@@ -56,6 +57,7 @@ class _Request:
     float16k: bool = False  # a file request whose decoding also fills wav16_float (a HuBERT configuration)
     key_shift: float = 0.0  # semitones on top of the shift to the singer's F0 median
     k_step: object = None   # shallow diffusion: the sampler starts from the clip's own mel at this step (None: full)
+    k_step_mel: str = "source"  # that start mel: the clip's own ("source") or its key-shifted one ("shifted")
 
 
 class SVCServer:
@@ -85,20 +87,25 @@ class SVCServer:
         self._worker = threading.Thread(target=self._run, name="svc-server", daemon=True)
         self._worker.start()
 
-    def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None, key_shift=0.0, k_step=None) -> Future:
+    def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None, key_shift=0.0, k_step=None,
+               k_step_mel="source") -> Future:
         """Queue one utterance (device tensors: 24 kHz f32 [N], 16 kHz [N16], optional float 16 kHz for
         ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True).
         key_shift: semitones for this request, on top of the shift to its singer's F0 median.
         k_step: shallow diffusion for this request (SVCPipeline.convert_ragged(k_step=)); a batch holds requests of
-        one k_step only, so the result is still the clip converted alone."""
+        one k_step only, so the result is still the clip converted alone.
+        k_step_mel: "source" or "shifted", shallow diffusion's start mel (SVCPipeline.convert(k_step_mel=)); a batch
+        holds one value of it too."""
         n = int(wav24.shape[-1])
         if n < 1 or int(wav16.shape[-1]) < 1:
             raise ValueError("SVCServer.submit: empty audio")
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
+        check_k_step_mel(k_step_mel, k_step)
         req = _Request(wav24=wav24.reshape(-1), wav16=wav16.reshape(-1), singer=int(singer),
                        utt_id=next(self._ids) if utt_id is None else int(utt_id),
                        wav16_float=None if wav16_float is None else wav16_float.reshape(-1),
-                       frames=self._frames(n), t_submit=time.monotonic(), key_shift=float(key_shift), k_step=k_step)
+                       frames=self._frames(n), t_submit=time.monotonic(), key_shift=float(key_shift), k_step=k_step,
+                       k_step_mel=k_step_mel)
         if wav24.is_cuda:
             req.stream = torch.cuda.current_stream(wav24.device)
             req.ready = torch.cuda.Event()
@@ -110,7 +117,7 @@ class SVCServer:
             self._cv.notify()
         return req.future
 
-    def submit_file(self, src, singer, utt_id=None, key_shift=0.0, k_step=None) -> Future:
+    def submit_file(self, src, singer, utt_id=None, key_shift=0.0, k_step=None, k_step_mel="source") -> Future:
         """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
         the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
         the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
@@ -118,11 +125,13 @@ class SVCServer:
         When the configuration names a HuBERT / ContentVec content type the decode also gives the request its float
         16 kHz row (audio.load_contentvec_audio of the file), so for batching it counts as a request with `wav16_float`:
         it shares a batch with tensor requests that carry one, never with tensor requests that do not.
-        k_step: as in submit()."""
+        k_step, k_step_mel: as in submit()."""
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
+        check_k_step_mel(k_step_mel, k_step)
         req = self._file_request(src, singer, utt_id)
         req.key_shift = float(key_shift)
         req.k_step = k_step
+        req.k_step_mel = k_step_mel
         if req.future.done():
             return req.future
         if torch.cuda.is_available():
@@ -173,14 +182,15 @@ class SVCServer:
     # ------------------------------------------------------------------ worker
     def _take_batch(self):
         """The oldest request plus the pending ones of compatible length (within length_ratio, same ContentVec input
-        form, same k_step), at most max_batch; called with the lock held."""
+        form, same k_step and k_step_mel), at most max_batch; called with the lock held."""
         head = self._pending[0]
         lo, hi = head.frames / self.length_ratio, head.frames * self.length_ratio
         batch = [head]
         for r in self._pending[1:]:
             if len(batch) == self.max_batch:
                 break
-            if lo <= r.frames <= hi and self._has_float(r) == self._has_float(head) and r.k_step == head.k_step:
+            if (lo <= r.frames <= hi and self._has_float(r) == self._has_float(head) and r.k_step == head.k_step
+                    and r.k_step_mel == head.k_step_mel):
                 batch.append(r)
         taken = set(map(id, batch))
         self._pending = [r for r in self._pending if id(r) not in taken]
@@ -256,6 +266,8 @@ class SVCServer:
                 kw["key_shift"] = [r.key_shift for r in batch]
             if batch[0].k_step is not None:  # the whole batch's (_take_batch)
                 kw["k_step"] = batch[0].k_step
+            if batch[0].k_step_mel != "source":
+                kw["k_step_mel"] = batch[0].k_step_mel
             wavs = self.pipeline.convert_ragged([r.wav24 for r in batch], [r.wav16 for r in batch],
                                                 [r.singer for r in batch], wavs16_float=w16f,
                                                 utt_ids=[r.utt_id for r in batch], **kw)
