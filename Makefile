@@ -34,6 +34,12 @@ build/mel_keyshift.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) inc
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
 	@python3 tools/check_kernel_resources.py build/$*.res mel_keyshift_kernel 256 || { rm -f $@; exit 1; }
 
+# the loudness stage streams f64 sqrt / pow / division over every sample: a spill would put scratch traffic beside it
+build/loudness.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include/svc_hip.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
+	@python3 tools/check_kernel_resources.py build/$*.res 'loudness_(power|apply)_kernel' 128 || { rm -f $@; exit 1; }
+
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -o $@
 

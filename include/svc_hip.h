@@ -31,6 +31,8 @@
  *                          rows HuBERT / ContentVec reads, from the launch that writes Whisper's rows
  *   svc_pcm16           <- utils/util.py:20-37 save_audio (peak normalisation, silence, 16-bit samples; the file
  *                          itself is written on the host)
+ *   svc_loudness_match  <- no counterpart in the reference: so-vits-svc's loudness envelope adjustment, between
+ *                          svc_bigvgan and svc_pcm16 (the output takes the source's slow RMS envelope)
  *
  * Conventions
  *   - Tensors are caller-owned DEVICE buffers, time-major: row = b*T + t, channels contiguous.
@@ -388,6 +390,37 @@ int64_t svc_pcm16_len(int64_t n_samples, int fs, int add_silence);
      - non-finite input is the caller's error and gives undefined samples (as for svc_whisper_encode). */
 svc_status svc_pcm16(svc_ctx* ctx, const float* wav, int B, int64_t S, const int64_t* utt_samples, int fs,
                      int add_silence, int turn_up, double volume_peak, void* pcm, float* peak_out, void* stream);
+
+/* host-only: 1 + n_out / hop; -1 for n_out < 0 or hop < 1 */
+int64_t svc_loudness_frames(int64_t n_out, int hop);
+
+/* Loudness envelope transfer (so-vits-svc's "loudness envelope adjustment"; opt-in, between svc_bigvgan and svc_pcm16).
+   wav f32 [B][S] (the vocoder output), src f32 [B][S_src] (the source at the same rate and time origin: sample i of
+   one lines up with sample i of the other) -> out f32 [B][S]. Per utterance, with n_out / n_src its own lengths,
+   W = window, H = hop:
+     K = svc_loudness_frames(n_out, H) frames for both signals; frame k covers samples [kH - W/2, kH - W/2 + W), a
+     sample outside [0, n) of its signal counting as 0 (librosa's rms(center=True) with zero padding);
+     P_k = (sum (double)s^2) / W, E_k = sqrt(P_k); g_k = pow(E_src_k / max(E_out_k, floor_rms), 1 - mix), then
+     min(g_k, max_gain) when max_gain > 0 (a value <= 0 means no cap), all in f64;
+     out[i] = (float)((double)wav[i] * (g_k0 + frac * (g_k1 - g_k0))), k0 = i / H, frac = (i - k0 H) / H,
+     k1 = min(k0 + 1, K - 1), for i < n_out; zeros from n_out to S.
+   This is audio.loudness_match, the project's host restatement: gains within (W + 16) * 2^-52 relative of it, samples
+   within 1 f32 ulp. mix = 1 copies wav bit for bit; mix = 0 gives it the source's envelope. A silent source frame
+   gives gain 0 (mix < 1); a silent output under a loud source is bounded by floor_rms, and by max_gain when given.
+   utt_samples / src_samples (host int64 [B] or NULL = S / S_src each; 0 <= n_out <= S, 0 <= n_src <= S_src): ragged
+   batch, see "Ragged batches"; each frame's sum runs in an order fixed by the utterance's own lengths, W and H, so an
+   utterance's row is bit-identical to the same utterance converted alone.
+   gain_out: optional device f64 [B][svc_loudness_frames(S, hop)], each utterance's g_k and 0 past its own K.
+   out may be wav itself (the same pointer); any other overlap of out with wav, and any with src, is an error. All
+   buffers need 4-byte alignment only (gain_out 8). The context need not be finalized. Two launches whatever B is; the
+   length tables and the frame powers go through a ring of this entry point's own, so the call may run on any stream.
+   SVC_ERR_INVALID before any HIP call: null wav, src or out; B < 1, S or S_src < 1; a length outside [0, S] /
+   [0, S_src]; window or hop < 1; mix outside [0, 1] or NaN; floor_rms not > 0; out overlapping wav partially, or src;
+   more than 64 MiB of frame powers (16 B * K * B: a hop far too small for the batch).
+   Non-finite input is the caller's error and gives undefined samples. */
+svc_status svc_loudness_match(svc_ctx* ctx, const float* wav, const float* src, int B, int64_t S, int64_t S_src,
+                              const int64_t* utt_samples, const int64_t* src_samples, int window, int hop, double mix,
+                              double floor_rms, double max_gain, float* out, double* gain_out, void* stream);
 
 /* ---------------- op-level entry points (used by the parity tests; weights are unpacked f32 device arrays) */
 /* y[B*T_out][Cout] = conv1d(x[B*T_in][Cin]) ; w [Cout][Cin][k] ; act 0 none / 1 gelu / 2 relu */

@@ -60,6 +60,9 @@ PROTOTYPES = {
     "svc_pcm16_len": (c_int64, [c_int64, c_int, c_int]),
     "svc_pcm16": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int, c_int, c_double, c_void_p,
                           c_void_p, c_void_p]),
+    "svc_loudness_frames": (c_int64, [c_int64, c_int]),
+    "svc_loudness_match": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int,
+                                   c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "svc_op_conv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_void_p, c_void_p]),
     "svc_op_conv_transpose1d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -17,6 +17,7 @@ librosa.load).
 """
 import collections
 import ctypes
+import math
 import os
 import struct
 
@@ -236,6 +237,75 @@ def to_pcm16(waveform, fs, add_silence=True, turn_up=True, volume_peak=0.9):
         sil = np.zeros((fs // 20,), dtype=w.dtype)
         w = np.concatenate([sil, w, sil])
     return np.clip(np.round(w.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+
+
+def loudness_params(fs=None, window=None, hop=None):
+    """(window, hop) of the loudness envelope: so-vits-svc's defaults fs // 2 * 2 and fs // 2 (a one-second frame
+    every half second) for whichever is None, which then needs fs."""
+    if (window is None or hop is None) and fs is None:
+        raise ValueError("loudness_match: give fs, or both window and hop")
+    window = int(fs) // 2 * 2 if window is None else int(window)
+    hop = int(fs) // 2 if hop is None else int(hop)
+    if window < 1 or hop < 1:
+        raise ValueError(f"loudness_match: window {window}, hop {hop}: both >= 1")
+    return window, hop
+
+
+def check_loudness_mix(mix):
+    """loudness_mix as a float in [0, 1], else ValueError before any device work; None (the stage is not run) stays
+    None."""
+    if mix is None:
+        return None
+    ok = isinstance(mix, (int, float, np.integer, np.floating)) and not isinstance(mix, (bool, np.bool_))
+    if not ok or not 0.0 <= float(mix) <= 1.0:  # NaN fails both comparisons
+        raise ValueError(f"loudness_mix {mix!r}: a number in [0, 1] (0: the source's envelope, 1: unchanged)")
+    return float(mix)
+
+
+def _frame_rms(s, K, window, hop):
+    """E_k, k < K: frame k covers samples [k hop - window // 2, .. + window) of s (f64), zero outside [0, len(s))."""
+    E = np.zeros(K, dtype=np.float64)
+    for k in range(K):
+        lo = k * hop - window // 2
+        seg = s[max(lo, 0):max(min(lo + window, len(s)), 0)]
+        E[k] = np.sqrt(math.fsum(seg * seg) / window)
+    return E
+
+
+def loudness_gains(y, x, fs=None, window=None, hop=None, mix=0.0, floor_rms=1e-6, max_gain=None):
+    """The per-frame gains g_k, f64 [1 + len(y) // hop], of loudness_match (its arguments)."""
+    window, hop = loudness_params(fs, window, hop)
+    mix = check_loudness_mix(mix)
+    if mix is None or not floor_rms > 0:
+        raise ValueError("loudness_match: mix in [0, 1] and floor_rms > 0")
+    y = np.asarray(y, dtype=np.float32).reshape(-1).astype(np.float64)
+    x = np.asarray(x, dtype=np.float32).reshape(-1).astype(np.float64)
+    K = 1 + len(y) // hop
+    E1, E2 = _frame_rms(x, K, window, hop), _frame_rms(y, K, window, hop)
+    g = (E1 / np.maximum(E2, float(floor_rms))) ** (1.0 - mix)
+    if max_gain is not None and max_gain > 0:
+        g = np.minimum(g, float(max_gain))
+    return g
+
+
+def loudness_match(y, x, fs=None, window=None, hop=None, mix=0.0, floor_rms=1e-6, max_gain=None):
+    """Loudness envelope transfer for one clip (so-vits-svc's "loudness envelope adjustment", per-frame form; DESIGN.md
+    "Loudness envelope transfer"): the output y f32 [n_out] takes the slow RMS envelope of the source x f32 [n_src]
+    (same rate and time origin) -> f32 [n_out]. The definition svc_loudness_match is tested against, f64 inside:
+      K = 1 + n_out // hop frames for both signals; frame k covers samples [k hop - window // 2, .. + window), zero
+      outside the signal (librosa's rms(center=True) with zero padding); E_k = sqrt(sum s^2 / window);
+      g_k = (E_x_k / max(E_y_k, floor_rms)) ** (1 - mix), then min(g_k, max_gain) with a max_gain > 0;
+      out[i] = f32(y[i] * (g_k0 + frac * (g_k1 - g_k0))), k0 = i // hop, frac = (i - k0 hop) / hop,
+      k1 = min(k0 + 1, K - 1).
+    mix = 1 returns y; mix = 0 gives y the source's envelope. window / hop default to fs // 2 * 2 and fs // 2."""
+    window, hop = loudness_params(fs, window, hop)
+    g = loudness_gains(y, x, None, window, hop, mix, floor_rms, max_gain)
+    y = np.asarray(y, dtype=np.float32).reshape(-1)
+    i = np.arange(len(y), dtype=np.int64)
+    k0 = i // hop
+    frac = (i - k0 * hop).astype(np.float64) / float(hop)
+    k1 = np.minimum(k0 + 1, len(g) - 1)
+    return (y.astype(np.float64) * (g[k0] + frac * (g[k1] - g[k0]))).astype(np.float32)
 
 
 def write_wav_pcm16(path, pcm, fs):

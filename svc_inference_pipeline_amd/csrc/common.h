@@ -270,16 +270,17 @@ struct StageRing {
   hipEvent_t ev[kRing] = {};
   int next = 0;
   int last = -1;  // slot handed out by the latest put(), until retire()
-  // copies `bytes` from `src` to device memory owned by the ring; *dev receives it
-  int put(const void* src, size_t bytes, hipStream_t s, void** dev) {
+  // copies `bytes` from `src` to device memory owned by the ring; *dev receives it. `extra`: device bytes kept behind
+  // the copied table in the same slot, not written here (scratch that the call's own kernels fill)
+  int put(const void* src, size_t bytes, hipStream_t s, void** dev, size_t extra = 0) {
     const int k = next;
     next = (next + 1) % kRing;
     if (ev[k]) SVC_HIP_CHECK(hipEventSynchronize(ev[k]));
     else SVC_HIP_CHECK(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-    if (cap[k] < bytes) {
+    if (cap[k] < bytes + extra) {
       if (h[k]) SVC_HIP_CHECK(hipHostFree(h[k]));
       if (d[k]) SVC_HIP_CHECK(hipFree(d[k]));
-      const size_t want = std::max<size_t>(bytes, 4096);
+      const size_t want = std::max<size_t>(bytes + extra, 4096);
       SVC_HIP_CHECK(hipHostMalloc(&h[k], want, hipHostMallocDefault));
       SVC_HIP_CHECK(hipMalloc(&d[k], want));
       cap[k] = want;

@@ -271,6 +271,7 @@ svc_status svc_ctx_destroy(svc_ctx* c) {
   c->lens_feat.release();
   c->lens_main.release();
   c->lens_pcm.release();
+  c->lens_loud.release();
   c->lens_load.release();
   delete c;
   return SVC_OK;

@@ -96,6 +96,11 @@ int f0_pyin(const float* wav, int B, int64_t ld, const int64_t* nvalid_dev, cons
 size_t pcm16_table_bytes(int B);
 int pcm16(const float* wav, int B, int64_t S, void* table, int64_t max_nb, int sil, int64_t L, int turn_up,
           double volume_peak, int16_t* pcm, float* peak_out, int need_peak, hipStream_t s);
+size_t loudness_lens_bytes(int B);
+size_t loudness_power_bytes(int B, int64_t K_max);
+int loudness_match(const float* wav, const float* src, int B, int64_t S, int64_t S_src, void* table, int64_t K_max,
+                   int window, int hop, double mix, double floor_rms, double max_gain, float* out, double* gain_out,
+                   int64_t K_out, hipStream_t s);
 int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
              const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
              float* y_src, int sr_mono, int64_t S_mono, float* y_mono, float* y_mono_float, bool ex, int32_t* info,

@@ -309,6 +309,49 @@ svc_status svc_pcm16(svc_ctx* c, const float* wav, int B, int64_t S, const int64
                reinterpret_cast<int16_t*>(pcm), peak_out, (turn_up || peak_out) ? 1 : 0, s);
 }
 
+// ---------------------------------------------------------------------------- loudness envelope transfer
+svc_status svc_loudness_match(svc_ctx* c, const float* wav, const float* src, int B, int64_t S, int64_t S_src,
+                              const int64_t* utt_samples, const int64_t* src_samples, int window, int hop, double mix,
+                              double floor_rms, double max_gain, float* out, double* gain_out, void* stream) {
+  SVC_REQUIRE(c, "loudness_match: null context");
+  SVC_REQUIRE(wav && src && out, "loudness_match: null %s", !wav ? "wav" : !src ? "src" : "out");
+  SVC_REQUIRE(B >= 1 && S >= 1 && S_src >= 1, "loudness_match: B=%d S=%lld S_src=%lld", B, (long long)S,
+              (long long)S_src);
+  SVC_REQUIRE(window >= 1 && hop >= 1, "loudness_match: window=%d hop=%d", window, hop);
+  SVC_REQUIRE(mix >= 0.0 && mix <= 1.0, "loudness_match: mix %g (must lie in [0, 1])", mix);
+  SVC_REQUIRE(floor_rms > 0.0, "loudness_match: floor_rms %g (must be positive)", floor_rms);
+  {  // out is wav itself or shares no byte with it (a block reads only the samples it writes), and none with src
+    const uintptr_t w0 = reinterpret_cast<uintptr_t>(wav), o0 = reinterpret_cast<uintptr_t>(out);
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(src);
+    const uintptr_t nb = (uintptr_t)B * (uintptr_t)S * 4, nr = (uintptr_t)B * (uintptr_t)S_src * 4;
+    SVC_REQUIRE(o0 == w0 || o0 + nb <= w0 || w0 + nb <= o0, "loudness_match: out overlaps wav without being wav");
+    SVC_REQUIRE(o0 + nb <= r0 || r0 + nr <= o0, "loudness_match: out overlaps src");
+  }
+  // one staged table (loudness.hip): int64 n_out[B], int64 n_src[B]; the frame powers lie behind it in the same slot
+  std::vector<int64_t> lens((size_t)2 * B);
+  int64_t max_n = 0;
+  for (int b = 0; b < B; ++b) {
+    lens[b] = utt_samples ? utt_samples[b] : S;
+    lens[B + b] = src_samples ? src_samples[b] : S_src;
+    SVC_REQUIRE(lens[b] >= 0 && lens[b] <= S, "loudness_match: utterance %d: %lld samples (batch length %lld)", b,
+                (long long)lens[b], (long long)S);
+    SVC_REQUIRE(lens[B + b] >= 0 && lens[B + b] <= S_src,
+                "loudness_match: utterance %d: %lld source samples (batch length %lld)", b, (long long)lens[B + b],
+                (long long)S_src);
+    max_n = std::max(max_n, lens[b]);
+  }
+  const int64_t K_max = 1 + max_n / hop;
+  SVC_REQUIRE(loudness_power_bytes(B, K_max) <= ((size_t)64 << 20),
+              "loudness_match: %lld frames x %d utterances: hop %d too small for this batch", (long long)K_max, B, hop);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_loud, s);
+  void* dev = nullptr;
+  if (int st = c->lens_loud.put(lens.data(), loudness_lens_bytes(B), s, &dev, loudness_power_bytes(B, K_max))) return st;
+  return loudness_match(wav, src, B, S, S_src, dev, K_max, window, hop, mix, floor_rms, max_gain, out, gain_out,
+                        1 + S / hop, s);
+}
+
 // ---------------------------------------------------------------------------- wav payloads -> the input batches (A1)
 svc_status svc_load_pcm(svc_ctx* c, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
                         const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,

@@ -95,10 +95,11 @@ def resynth_files(engine, cfg, wav_paths):
 
 
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                 f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
+                 f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
+                 loudness_mix=None):
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
     the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16). k_step, k_step_mel: shallow diffusion
-    and its start mel (SVCPipeline.convert)."""
+    and its start mel; loudness_mix: loudness envelope transfer (SVCPipeline.convert)."""
     # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
     wav16f = None
     if wants_float16k(cfg):  # and utils/hubert.py:137-143's float 16 kHz copy from the same stage
@@ -115,12 +116,14 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
                                       wav16_float=None if wav16f is None else wav16f[None].contiguous(),
                                       pcm16=pcm16, key_shift=key_shift,
                                       **({} if k_step is None else dict(k_step=k_step)),
-                                      **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)))
+                                      **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
+                                      **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)))
     return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
-                  f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
+                  f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
+                  loudness_mix=None):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
     list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
     pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
@@ -136,7 +139,8 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
     wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), wavs16_float=w16f,
                                             fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16,
                                             key_shift=key_shift, **({} if k_step is None else dict(k_step=k_step)),
-                                            **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)))
+                                            **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
+                                            **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)))
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
     return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
@@ -168,6 +172,9 @@ def build_parser():
                     help="with --k-step, the mel the sampler starts from: the source's own, or 'shifted': its "
                          "key-shifted mel, moved by the same factor as the F0 (singer median and --key), so that its "
                          "harmonics sit where the conditioner's pitch asks for them")
+    ap.add_argument("--loudness-mix", type=float, default=None, metavar="X",
+                    help="loudness envelope transfer: the converted voice takes the source's slow RMS envelope; 0 "
+                         "gives it the source's envelope, 1 leaves it unchanged (default: the step is not run)")
     ap.add_argument("--resynth", action="store_true",
                     help="copy-synthesis: each file's own mel through the vocoder alone (judges a vocoder checkpoint; "
                          "needs no mapper or content checkpoint); output gen/<wav stem>_resynth.wav")
@@ -227,6 +234,10 @@ def main(argv=None):
         check_k_step_mel(args.k_step_mel, args.k_step)
     except ValueError:
         ap.error("--k-step-mel shifted needs --k-step")
+    try:
+        A.check_loudness_mix(args.loudness_mix)
+    except ValueError as exc:
+        ap.error(f"--loudness-mix: {exc}")
     print("Loading mapper and vocoder...", flush=True)
     hubert = args.hubert_ckpt or getattr(cfg, "contentVec_model", None)
     engine = build_engine(cfg, args.device, mapper, vocoder, args.whisper_ckpt, args.random_weights, args.seed,
@@ -248,11 +259,11 @@ def main(argv=None):
     if len(args.wav) == 1:
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
-                                k_step_mel=args.k_step_mel)]
+                                k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix)]
     else:
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
-                                k_step_mel=args.k_step_mel)
+                                k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix)
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
     for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU

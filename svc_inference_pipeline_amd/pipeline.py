@@ -28,6 +28,7 @@ from dataclasses import dataclass
 
 import torch
 
+from .audio import check_loudness_mix
 from .runtime import SVCEngine, check_k_step, check_k_step_mel, mel_frames
 
 WHISPER_WINDOW = 478720       # 16 kHz samples per long-input window (29.92 s)
@@ -216,7 +217,8 @@ class SVCPipeline:
         return self._side
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
-                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
+                noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
+                loudness_mix=None):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
         Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
         save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`.
@@ -226,19 +228,23 @@ class SVCPipeline:
         x_T is not used then.
         k_step_mel (with k_step): "source" (default) starts from the clip's own mel; "shifted" from its key-shifted mel
         (SVCEngine.mel_keyshift by the factor shift_f0 applies, SVCEngine.pitch_factor), so the start state's harmonics
-        sit at the pitch the conditioner asks for. ConvertResult.mel stays the unshifted source mel."""
+        sit at the pitch the conditioner asks for. ConvertResult.mel stays the unshifted source mel.
+        loudness_mix (None: the stage is not run, the call as before): loudness envelope transfer between the vocoder
+        and the sample conversion (SVCEngine.loudness_match against wav24, in place): 0 gives the converted voice the
+        source's slow RMS envelope, 1 leaves it as it is; `wav` and `pcm` are the adjusted ones."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
+        loudness_mix = check_loudness_mix(loudness_mix)
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
-                                 wav16_float, pcm16, key_shift, k_step, k_step_mel == "shifted")
+                                 wav16_float, pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix)
 
     def _check_k_step(self, k_step):
         """k_step validated against the engine's schedule (ValueError before any device work); None stays None."""
         return None if k_step is None else check_k_step(k_step, getattr(self.engine, "cfg", None))
 
     def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
-                 pcm16=False, key_shift=0.0, k_step=None, shifted=False):
+                 pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -272,10 +278,13 @@ class SVCPipeline:
             x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, noise=noise, seed=seed,
                                   utt_ids=utt_ids, k_step=k_step, mel_src=mel_src)
         wav = e.bigvgan(x0)
+        if loudness_mix is not None:  # T * hop <= N: every clip's source covers its output
+            e.loudness_match(wav, wav24, mix=loudness_mix, out=wav)
         return ConvertResult(wav=wav, mel=mel, f0=f0, x0=x0, pcm=e.pcm16(wav) if pcm16 else None)
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
+                     utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
+                     loudness_mix=None):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -287,11 +296,15 @@ class SVCPipeline:
         pcm16=True: each waveform comes back as save_audio's samples instead, int16 [T_i*hop + 2*(fs//20)]
         (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak).
         key_shift: semitones, a scalar or one per utterance (shift_f0).
-        k_step, k_step_mel: shallow diffusion for the whole batch and its start mel, as in convert()."""
+        k_step, k_step_mel: shallow diffusion for the whole batch and its start mel, as in convert().
+        loudness_mix: loudness envelope transfer for the whole batch, as in convert() (both routes)."""
         k_step = self._check_k_step(k_step)
-        shallow = {} if k_step is None else dict(k_step=k_step)
+        shallow = {} if k_step is None else dict(k_step=k_step)  # and the other keywords that are left out when unset
         if check_k_step_mel(k_step_mel, k_step) != "source":
             shallow["k_step_mel"] = k_step_mel
+        loudness_mix = check_loudness_mix(loudness_mix)
+        if loudness_mix is not None:
+            shallow["loudness_mix"] = loudness_mix
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
             raise ValueError("convert_many: wavs24, wavs16, singers (and wavs16_float) must have one entry per utterance")
@@ -385,31 +398,36 @@ class SVCPipeline:
         return out
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source"):
+                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
         [T_b * hop + 2 * (fs // 20)] (svc_pcm16 with the same lengths). Each clip's F0 moves onto its own singer's
         median (shift_f0), then up by key_shift semitones (a scalar or one per clip). k_step: shallow diffusion, as in
         convert(): each clip starts from its own mel (k_step_mel="shifted": its own key-shifted mel, by its own factor),
-        noised with its own utterance id's draw."""
+        noised with its own utterance id's draw. loudness_mix: loudness envelope transfer, as in convert(): each
+        clip's T_b * hop output samples against its own 24 kHz source (svc_loudness_match with both length tables),
+        before the sample conversion."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
+        loudness_mix = check_loudness_mix(loudness_mix)
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                                        pcm16, key_shift, k_step, k_step_mel == "shifted")
+                                        pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix)
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
-                      float16k=None, key_shift=0.0, k_step=None, k_step_mel="source"):
+                      float16k=None, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
         HuBERT / ContentVec reads them as `wavs16_float`, what utils/hubert.py:137-143 feeds it; None (default): when
         the configuration names a HuBERT content type (wants_float16k); False: HuBERT is fed Whisper's int16-grid rows.
-        Without a HuBERT type and with None or False, load_batch is called without the keyword."""
+        Without a HuBERT type and with None or False, load_batch is called without the keyword.
+        loudness_mix: as in convert_ragged(), against the 24 kHz rows the load stage wrote."""
         from . import audio as A
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
+        loudness_mix = check_loudness_mix(loudness_mix)
         if wants_float16k(self.engine.cfg) if float16k is None else float16k:
             wavs24, wavs16, wavs16_float = A.load_batch(sources, self.engine.cfg.fs, self.engine, float16k=True)
         else:
@@ -418,10 +436,11 @@ class SVCPipeline:
         return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float, fast_inference=fast_inference,
                                    speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift,
                                    **({} if k_step is None else dict(k_step=k_step)),
-                                   **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)))
+                                   **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
+                                   **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)))
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                        pcm16=False, key_shift=0.0, k_step=None, shifted=False):
+                        pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -454,6 +473,8 @@ class SVCPipeline:
                               **shallow)
         wav = e.bigvgan(x0, frames=T_b)
         hop = e.cfg.hop_length
+        if loudness_mix is not None:
+            e.loudness_match(wav, w24, n_samples=[t * hop for t in T_b], src_samples=n24, mix=loudness_mix, out=wav)
         if pcm16:
             pcm = e.pcm16(wav, n_samples=[t * hop for t in T_b])
             sil2 = pcm.shape[1] - wav.shape[1]  # both silences

@@ -559,3 +559,36 @@ class SVCEngine:
                   int(self.cfg.fs), 1 if add_silence else 0, 1 if turn_up else 0, float(volume_peak), _ptr(pcm),
                   _ptr(peak), _stream())
         return (pcm, peak) if return_peak else pcm
+
+    def loudness_match(self, wav, src, n_samples=None, src_samples=None, mix=0.0, window=None, hop=None,
+                       floor_rms=1e-6, max_gain=None, out=None, return_gain=False):
+        """Loudness envelope transfer on the device (svc_loudness_match; audio.loudness_match per utterance: gains
+        within (window + 16) * 2^-52 relative, samples within 1 f32 ulp): wav f32 [B, S] (the vocoder output) takes the
+        slow RMS envelope of src f32 [B, S_src] (the source at the same rate and time origin) -> f32 [B, S]. mix: 0
+        gives the source's envelope, 1 leaves wav as it is. window / hop default to fs // 2 * 2 and fs // 2
+        (so-vits-svc's). n_samples / src_samples (ragged batch, host ints [B]): utterance b is wav[b, :n_samples[b]]
+        against src[b, :src_samples[b]]; its row is zeros from n_samples[b] on. max_gain: a cap on the per-frame gain
+        (None: none). out: the result's tensor, which may be wav itself (in place). return_gain: also the f64
+        [B, 1 + S // hop] per-frame gains (0 past an utterance's own frames)."""
+        from .audio import check_loudness_mix, loudness_params
+        if wav.dim() != 2 or wav.dtype != torch.float32 or src.dim() != 2 or src.dtype != torch.float32:
+            raise ValueError("loudness_match: wav and src must be f32 [B, S] and [B, S_src]")
+        if src.shape[0] != wav.shape[0]:
+            raise ValueError(f"loudness_match: {src.shape[0]} source rows for a batch of {wav.shape[0]}")
+        mix = check_loudness_mix(mix)
+        if mix is None:
+            raise ValueError("loudness_match: mix is None")
+        window, hop = loudness_params(int(self.cfg.fs), window, hop)
+        B, S = wav.shape
+        if out is None:
+            out = torch.empty_like(wav)
+        elif out.shape != wav.shape or out.dtype != torch.float32:
+            raise ValueError("loudness_match: out must be f32 with wav's shape")
+        gain = None
+        if return_gain:
+            gain = torch.empty(B, int(_lib.load().svc_loudness_frames(S, hop)), device=wav.device, dtype=torch.float64)
+        _lib.call("svc_loudness_match", self._ctx, _ptr(wav), _ptr(src), B, S, src.shape[1],
+                  _host_lengths(n_samples, B, ctypes.c_int64), _host_lengths(src_samples, B, ctypes.c_int64), window,
+                  hop, mix, float(floor_rms), 0.0 if max_gain is None else float(max_gain), _ptr(out), _ptr(gain),
+                  _stream())
+        return (out, gain) if return_gain else out

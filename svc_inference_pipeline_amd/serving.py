@@ -15,7 +15,8 @@ it (so padding stays bounded: the kernels skip the padded tail, but its rows sti
 carries an utterance id (given, or a running counter) that keys its device noise, so its waveform is bit-identical to
 converting that clip alone with the same id, whatever it was batched with (tests/test_gpu_ragged.py). A request may ask
 for shallow diffusion (`k_step`, and `k_step_mel` for its start mel); a batch is formed only from requests with the same
-`k_step` and `k_step_mel`.
+`k_step` and `k_step_mel`. The same holds for `loudness_mix` (loudness envelope transfer against the request's own
+24 kHz source).
 
 Streams: submit() records an event on the caller's current stream, and the worker's stream waits for it before it
 reads the request's tensors, so inputs produced by kernels still in flight on the caller's stream are safe to
@@ -58,6 +59,7 @@ class _Request:
     key_shift: float = 0.0  # semitones on top of the shift to the singer's F0 median
     k_step: object = None   # shallow diffusion: the sampler starts from the clip's own mel at this step (None: full)
     k_step_mel: str = "source"  # that start mel: the clip's own ("source") or its key-shifted one ("shifted")
+    loudness_mix: object = None  # loudness envelope transfer against the source (None: not run)
 
 
 class SVCServer:
@@ -88,24 +90,27 @@ class SVCServer:
         self._worker.start()
 
     def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None, key_shift=0.0, k_step=None,
-               k_step_mel="source") -> Future:
+               k_step_mel="source", loudness_mix=None) -> Future:
         """Queue one utterance (device tensors: 24 kHz f32 [N], 16 kHz [N16], optional float 16 kHz for
         ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True).
         key_shift: semitones for this request, on top of the shift to its singer's F0 median.
         k_step: shallow diffusion for this request (SVCPipeline.convert_ragged(k_step=)); a batch holds requests of
         one k_step only, so the result is still the clip converted alone.
         k_step_mel: "source" or "shifted", shallow diffusion's start mel (SVCPipeline.convert(k_step_mel=)); a batch
-        holds one value of it too."""
+        holds one value of it too.
+        loudness_mix: loudness envelope transfer for this request (SVCPipeline.convert_ragged(loudness_mix=)); a batch
+        holds requests of one value only (None, the stage not run, is a value of its own)."""
         n = int(wav24.shape[-1])
         if n < 1 or int(wav16.shape[-1]) < 1:
             raise ValueError("SVCServer.submit: empty audio")
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
         check_k_step_mel(k_step_mel, k_step)
+        loudness_mix = A.check_loudness_mix(loudness_mix)
         req = _Request(wav24=wav24.reshape(-1), wav16=wav16.reshape(-1), singer=int(singer),
                        utt_id=next(self._ids) if utt_id is None else int(utt_id),
                        wav16_float=None if wav16_float is None else wav16_float.reshape(-1),
                        frames=self._frames(n), t_submit=time.monotonic(), key_shift=float(key_shift), k_step=k_step,
-                       k_step_mel=k_step_mel)
+                       k_step_mel=k_step_mel, loudness_mix=loudness_mix)
         if wav24.is_cuda:
             req.stream = torch.cuda.current_stream(wav24.device)
             req.ready = torch.cuda.Event()
@@ -117,7 +122,8 @@ class SVCServer:
             self._cv.notify()
         return req.future
 
-    def submit_file(self, src, singer, utt_id=None, key_shift=0.0, k_step=None, k_step_mel="source") -> Future:
+    def submit_file(self, src, singer, utt_id=None, key_shift=0.0, k_step=None, k_step_mel="source",
+                    loudness_mix=None) -> Future:
         """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
         the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
         the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
@@ -125,10 +131,12 @@ class SVCServer:
         When the configuration names a HuBERT / ContentVec content type the decode also gives the request its float
         16 kHz row (audio.load_contentvec_audio of the file), so for batching it counts as a request with `wav16_float`:
         it shares a batch with tensor requests that carry one, never with tensor requests that do not.
-        k_step, k_step_mel: as in submit()."""
+        k_step, k_step_mel, loudness_mix: as in submit()."""
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
         check_k_step_mel(k_step_mel, k_step)
+        loudness_mix = A.check_loudness_mix(loudness_mix)
         req = self._file_request(src, singer, utt_id)
+        req.loudness_mix = loudness_mix
         req.key_shift = float(key_shift)
         req.k_step = k_step
         req.k_step_mel = k_step_mel
@@ -182,7 +190,7 @@ class SVCServer:
     # ------------------------------------------------------------------ worker
     def _take_batch(self):
         """The oldest request plus the pending ones of compatible length (within length_ratio, same ContentVec input
-        form, same k_step and k_step_mel), at most max_batch; called with the lock held."""
+        form, same k_step, k_step_mel and loudness_mix), at most max_batch; called with the lock held."""
         head = self._pending[0]
         lo, hi = head.frames / self.length_ratio, head.frames * self.length_ratio
         batch = [head]
@@ -190,7 +198,7 @@ class SVCServer:
             if len(batch) == self.max_batch:
                 break
             if (lo <= r.frames <= hi and self._has_float(r) == self._has_float(head) and r.k_step == head.k_step
-                    and r.k_step_mel == head.k_step_mel):
+                    and r.k_step_mel == head.k_step_mel and r.loudness_mix == head.loudness_mix):
                 batch.append(r)
         taken = set(map(id, batch))
         self._pending = [r for r in self._pending if id(r) not in taken]
@@ -268,6 +276,8 @@ class SVCServer:
                 kw["k_step"] = batch[0].k_step
             if batch[0].k_step_mel != "source":
                 kw["k_step_mel"] = batch[0].k_step_mel
+            if batch[0].loudness_mix is not None:
+                kw["loudness_mix"] = batch[0].loudness_mix
             wavs = self.pipeline.convert_ragged([r.wav24 for r in batch], [r.wav16 for r in batch],
                                                 [r.singer for r in batch], wavs16_float=w16f,
                                                 utt_ids=[r.utt_id for r in batch], **kw)
