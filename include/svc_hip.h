@@ -21,6 +21,7 @@
  *   svc_condition       <- modules/encoder.py:165-201 EncoderFramework.forward
  *   svc_diffsvc_sample  <- modules/diffsvcrepo_inference.py:154-240 svc_model_inference (DDPM or PLMS)
  *   svc_diffsvc_sample_from <- the same from noise level k_step - 1 (Diff-SVC's shallow diffusion)
+ *   svc_diffsvc_sample_steps <- DPM-Solver++(2M) / DDIM over a list of timesteps (not in the reference)
  *   svc_mel_normalize   <- utils/acoustic_feature_extraction.py:75-80 normalize_mel_channel
  *   svc_bigvgan         <- utils/acoustic_feature_extraction.py:83-97 denormalize_mel_channel
  *                          + modules/bigvgan_inference.py:29-44 synthesis_audios (Generator + trim + fade)
@@ -311,6 +312,27 @@ svc_status svc_diffsvc_sample_from(svc_ctx* ctx, const float* cond, int B, int T
                                    int interval, int k_step, const float* mel_src, const float* x_start,
                                    const float* noise, uint64_t seed, const int32_t* utt_ids, float* x0, void* stream);
 
+/* A multistep ODE solver over a caller-given list of timesteps: DPM-Solver++(2M) in the data-prediction form (order 2)
+   or its first-order case, DDIM at eta = 0 (order 1). timesteps: HOST int32 [n_steps], strictly decreasing, each in
+   [0, steps); the denoiser runs once per entry, so the call costs n_steps denoiser calls. With lambda_t =
+   ln(ac_t / (1 - ac_t)) / 2 over the context's f32 alphas_cumprod table and D_t = clip(sqrt(1 / ac_t) x -
+   sqrt(1 / ac_t - 1) eps, -1, 1) (the DDPM path's clip_denoised prediction), the step t -> s is
+     x_s = sqrt((1 - ac_s) / (1 - ac_t)) x_t - sqrt(ac_s) expm1(-h) Dbar,  h = lambda_s - lambda_t,
+   Dbar = D_t at order 1 and at the first step, else (1 + h / (2 h_prev)) D_t - h / (2 h_prev) D_prev; the last entry
+   returns x_0 = D_t (first order whatever `order` says). The start state at level timesteps[0] is x_start, or mel_src
+   noised forward as in svc_diffsvc_sample_from, or with neither the x_T draw of svc_diffsvc_sample; the last two draw
+   on the device and need utt_ids. Nothing is drawn per step. Which timesteps to take is the caller's policy (the
+   Python package's config.solver_timesteps spaces them evenly in lambda). SVC_ERR_INVALID: an empty list, one that is
+   not strictly decreasing, an entry outside [0, steps), an order other than 1 or 2, both start states, a device draw
+   without utt_ids. The sampler stage at B = 32 x 937 frames: PLMS at interval 10 (101 denoiser calls) 198.6 ms; order 2
+   over 50 / 20 / 10 log-SNR-spaced steps from noise 97.9 / 40.7 / 21.0 ms, over 20 / 10 from level 299 38.6 / 21.1 ms
+   (profiles/dpm_bench.json): time follows the call count. Output quality at a given n_steps has been checked on an
+   analytic Gaussian denoiser and on random weights only, no real checkpoint exists here. */
+svc_status svc_diffsvc_sample_steps(svc_ctx* ctx, const float* cond, int B, int T, const int32_t* frames,
+                                    const int32_t* timesteps, int n_steps, int order, const float* mel_src,
+                                    const float* x_start, uint64_t seed, const int32_t* utt_ids, float* x0,
+                                    void* stream);
+
 /* A13+A14+A15: x0 f32 [B*T][n_mel] (normalised) -> wav [B][T*256] f32 (denorm, Generator, tanh, fade-out).
    frames (host int32 [B] or NULL): ragged batch, utterance b's waveform is frames[b]*256 samples (fade-out at its end,
    zeros after).
@@ -504,6 +526,14 @@ svc_status svc_op_plms_update(const float* e0, const float* e1, const float* e2,
 svc_status svc_op_ddpm_update(float* x, const float* eps, int B, int T, int C, float sra, float srm1, float c1,
                               float c2, float sigma, const float* z, uint64_t seed, const int32_t* utt_ids, int step,
                               void* x16, int ld16, int bf16, void* stream);
+/* One DPM-Solver++(2M) / DDIM update in place on x [rows][C] (svc_diffsvc_sample_steps launches it after each denoise):
+ * D = clip(sra x - srm1 eps, -1, 1); Dbar = D, or with d_prev (NULL: no history) w0 D + w1 d_prev; x = a x + b Dbar, or
+ * with final_step x = D (a, b, w0, w1 and d_prev are ignored). d_out (optional) receives D and may be d_prev. x16 is
+ * optional. Four channels per thread when C % 4 == 0, ld16 % 4 == 0, the f32 pointers are 16-byte and x16 8-byte
+ * aligned, else one; both forms return the same bits. */
+svc_status svc_op_dpm_update(float* x, const float* eps, const float* d_prev, float* d_out, int rows, int C, float sra,
+                             float srm1, float w0, float w1, float a, float b, int final_step, uint16_t* x16, int ld16,
+                             int bf16, void* stream);
 /* The DiffSVC denoiser's steps one at a time, each through the launcher choice svc_diffsvc_eps / svc_diffsvc_sample
  * make for it (stage_diffsvc.hip diffsvc_*), selected as there by the op-level context's kernel switches
  * (svc_ctx_set_config(NULL, "tune.gate_ws" | "tune.gemm_variant" | "tune.res_proj" | "tune.diff_head" |

@@ -50,6 +50,8 @@ PROTOTYPES = {
                                    c_uint64, c_void_p, c_void_p, c_void_p]),
     "svc_diffsvc_sample_from": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                         c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "svc_diffsvc_sample_steps": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                         c_void_p, c_uint64, c_void_p, c_void_p, c_void_p]),
     "svc_mel_normalize": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "svc_diffsvc_eps": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "svc_bigvgan": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -91,6 +93,8 @@ PROTOTYPES = {
     "svc_op_plms_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int,
                                    c_float, c_float, c_float, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                    c_int, c_int, c_int, c_void_p]),
+    "svc_op_dpm_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float,
+                                  c_float, c_float, c_float, c_int, c_void_p, c_int, c_int, c_void_p]),
     "svc_op_ddpm_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                    c_void_p, c_uint64, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "svc_op_diffsvc_gate": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,

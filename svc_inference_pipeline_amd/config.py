@@ -133,6 +133,60 @@ def noise_schedule(mapper_cfg):
     return np.linspace(a, b, int(n))
 
 
+SOLVERS = {"ddim": 1, "dpmpp2m": 2}  # solver name -> order of svc_diffsvc_sample_steps
+SOLVER_SPACINGS = ("logsnr", "uniform")
+
+
+def check_solver(solver, solver_steps=20, solver_spacing="logsnr"):
+    """The solver keywords of the sampler calls: solver None (the DDPM / PLMS call as before) or a name of SOLVERS,
+    solver_steps an int >= 1, solver_spacing a name of SOLVER_SPACINGS; else ValueError before any device work."""
+    if solver is None:
+        return None
+    if solver not in SOLVERS:
+        raise ValueError(f"solver {solver!r}: None, {', '.join(map(repr, SOLVERS))}")
+    ok = isinstance(solver_steps, (int, np.integer)) and not isinstance(solver_steps, bool)
+    if not ok or solver_steps < 1:
+        raise ValueError(f"solver_steps {solver_steps!r}: an integer >= 1")
+    if solver_spacing not in SOLVER_SPACINGS:
+        raise ValueError(f"solver_spacing {solver_spacing!r}: 'logsnr' or 'uniform'")
+    return solver
+
+
+def solver_timesteps(cfg, k_step, n, spacing="logsnr"):
+    """The timesteps of an n-step solver run (svc_diffsvc_sample_steps) from noise level K - 1 down, K = k_step or with
+    None the schedule's length: a strictly decreasing list of ints in [0, K - 1] that starts at K - 1.
+    "logsnr": evenly spaced in lambda_t = ln(ac_t / (1 - ac_t)) / 2 between lambda_{K-1} and lambda_0 and snapped to the
+    grid (node j is the first t nearest the j-th target; a node not below its predecessor is dropped, so the list may be
+    shorter than n). lambda is f64 over the engine's f32 alphas_cumprod table widened exactly. Evenly spaced t ends on a
+    last step of h = 2.9 (n = 20) in lambda with the linear beta schedule, which costs both orders their accuracy
+    (DESIGN.md).
+    "uniform": t_j = ((K - 1)(n - 1 - j)) // (n - 1).
+    The library sees only the list: this is the one place the policy lives."""
+    betas = noise_schedule(cfg.mapper)
+    steps = len(betas)
+    K = steps if k_step is None else int(k_step)
+    if not 1 <= K <= steps:
+        raise ValueError(f"k_step {k_step!r}: an integer in [1, {steps}]")
+    n_ok = isinstance(n, (int, np.integer)) and not isinstance(n, bool)
+    if not n_ok or n < 1 or n > K:
+        raise ValueError(f"solver_steps {n!r}: an integer in [1, {K}]")
+    if spacing not in SOLVER_SPACINGS:
+        raise ValueError(f"solver_spacing {spacing!r}: 'logsnr' or 'uniform'")
+    n = int(n)
+    if n == 1:
+        return [K - 1]
+    if spacing == "uniform":
+        return [((K - 1) * (n - 1 - j)) // (n - 1) for j in range(n)]
+    ac = np.cumprod(1.0 - betas).astype(np.float32).astype(np.float64)[:K]
+    lam = 0.5 * np.log(ac / (1.0 - ac))
+    out = []
+    for j in range(n):
+        t = int(np.argmin(np.abs(lam - (lam[K - 1] + (lam[0] - lam[K - 1]) * j / (n - 1)))))
+        if not out or t < out[-1]:
+            out.append(t)
+    return out
+
+
 def load_stats(cfg):
     path = os.path.join(getattr(cfg, "config_dir", CONFIG_DIR), cfg.stats_file)
     with open(path) as f:

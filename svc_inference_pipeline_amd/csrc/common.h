@@ -351,6 +351,28 @@ struct DdpmArgs {
   const float* z; uint64_t seed; const int* utt_ids; int step;
   int bf16;  // x16 holds bfloat16 operands
 };
+// One DPM-Solver++(2M) update in the data-prediction form, in place on x (stage_diffsvc.hip svc_diffsvc_sample_steps,
+// elementwise.hip dpm_update): D = clamp(sra x - srm1 eps, -1, 1), the DDPM path's clip_denoised prediction;
+// Dbar = D, or w0 D + w1 d_prev with a history; x' = a x + b Dbar, or D at the final step (sigma_next = 0). The first-
+// order case (no history) is DDIM at eta = 0.
+struct DpmArgs {
+  float* x;             // [rows][C], updated in place
+  const float* eps;     // [rows][C]
+  const float* d_prev;  // [rows][C] the previous step's D, or NULL: first order
+  float* d_out;         // [rows][C] receives D, or NULL; may be d_prev (an element is read before it is written)
+  float sra, srm1;      // the schedule's sqrt(1 / ac_t), sqrt(1 / ac_t - 1)
+  float w0, w1, a, b;
+  int final_step;       // x' = D; a, b, w0, w1 and d_prev are not used
+  f16* x16; int ld16;   // optional 16-bit operand copy of x', columns 0..C-1 of rows of ld16 halves
+  int bf16;
+};
+// The update of one element, the only arithmetic of both kernel forms (dpm_kernel, dpm4_kernel). Every multiply-add is
+// spelled as an fma and the other products stand alone, so contraction has no choice to make: the forms agree bit for bit.
+__device__ __forceinline__ void dpm_math(const DpmArgs& p, float x, float eps, float d_prev, float& d, float& x_out) {
+  d = fminf(fmaxf(fmaf(p.sra, x, -(p.srm1 * eps)), -1.0f), 1.0f);
+  const float dbar = p.d_prev ? fmaf(p.w0, d, p.w1 * d_prev) : d;
+  x_out = p.final_step ? d : fmaf(p.a, x, p.b * dbar);
+}
 // Shallow diffusion's start state (stage_diffsvc.hip svc_diffsvc_sample_from, elementwise.hip q_sample): the source
 // mel normalised per channel, y = (mel - mn) / (mx - mn + 1e-12) * 2 - 1 (utils/acoustic_feature_extraction.py:75-80,
 // no clamp), and noised forward, x = a y + b z with z given or drawn. noised = 0: x = y (svc_mel_normalize).

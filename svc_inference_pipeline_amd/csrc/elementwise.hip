@@ -1,6 +1,6 @@
 // Bandwidth-bound kernels of the SVC path on gfx950: LayerNorm (fp32 statistics), content mapping,
 // conditioner bucketize,
-// sampler updates (DDPM / PLMS), mel normalisation + q_sample, mel de-normalisation, conv_post+tanh+fade.
+// sampler updates (DDPM / PLMS / DPM-Solver++), mel normalisation + q_sample, mel de-normalisation, conv_post+tanh+fade.
 // All tensors are time-major [rows = b*T + t][channels].
 #include <cstdlib>
 #include <type_traits>
@@ -509,6 +509,71 @@ int plms_update(const PlmsArgs& p, int rows, int C, hipStream_t s) {
     hipLaunchKernelGGL(plms4_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, s, p, rows, C);
   else
     hipLaunchKernelGGL(plms_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, p, rows, C);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
+// DPM-Solver++(2M) / DDIM update (DpmArgs and dpm_math, common.h), in place on x, launched right after the head that
+// wrote eps. Four or five f32 streams and one 16-bit stream per element: HBM-bound, no LDS. A sampler call of N steps
+// costs N denoiser calls: at B = 32 x 937 frames 97.9 / 40.7 / 21.0 ms at N = 50 / 20 / 10 against PLMS-100's 198.6 ms
+// (profiles/dpm_bench.json). Output quality at N steps: checked on an analytic denoiser and random weights only.
+__global__ void dpm_kernel(DpmArgs p, int rows, int C) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)rows * C) return;
+  float d, xn;
+  dpm_math(p, p.x[i], p.eps[i], p.d_prev ? p.d_prev[i] : 0.f, d, xn);
+  if (p.d_out) p.d_out[i] = d;
+  p.x[i] = xn;
+  if (p.x16) {
+    const int64_t r = i / C;
+    const int c = (int)(i - r * C);
+    p.x16[r * p.ld16 + c] = enc16(xn, p.bf16);
+  }
+}
+
+// the same update on 4 consecutive channels per thread (C % 4 == 0, 16-B aligned rows): 16-B loads and stores, an 8-B
+// 16-bit store, a quarter of the threads; per element dpm_math, so the identical bits
+__global__ void dpm4_kernel(DpmArgs p, int rows, int C) {
+  const int64_t i4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int C4 = C >> 2;
+  if (i4 >= (int64_t)rows * C4) return;
+  const int64_t i = i4 * 4;
+  auto ld = [&](const float* q) { return *reinterpret_cast<const float4*>(q + i); };
+  const float4 x = ld(p.x), e = ld(p.eps);
+  const float4 dp = p.d_prev ? ld(p.d_prev) : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 d, xn;
+  dpm_math(p, x.x, e.x, dp.x, d.x, xn.x);
+  dpm_math(p, x.y, e.y, dp.y, d.y, xn.y);
+  dpm_math(p, x.z, e.z, dp.z, d.z, xn.z);
+  dpm_math(p, x.w, e.w, dp.w, d.w, xn.w);
+  if (p.d_out) *reinterpret_cast<float4*>(p.d_out + i) = d;
+  *reinterpret_cast<float4*>(p.x + i) = xn;
+  if (p.x16) {
+    const int64_t r = i4 / C4;
+    const int c = (int)(i4 - r * C4) * 4;
+    H4 pk;
+    const bool bf = p.bf16;
+    pk.h[0] = enc16(xn.x, bf); pk.h[1] = enc16(xn.y, bf); pk.h[2] = enc16(xn.z, bf); pk.h[3] = enc16(xn.w, bf);
+    *reinterpret_cast<uint2*>(p.x16 + r * p.ld16 + c) = pk.u;
+  }
+}
+
+// the 4-channel form's layout conditions (dpm4_kernel)
+static bool dpm_vec4_ok(const DpmArgs& p, int C) {
+  bool vec = C % 4 == 0 && (!p.x16 || p.ld16 % 4 == 0) && ((uintptr_t)p.x16 & 7) == 0;
+  const void* ptrs[] = {p.x, p.eps, p.d_prev, p.d_out};
+  for (const void* q : ptrs) vec = vec && ((uintptr_t)q & 15) == 0;
+  return vec;
+}
+
+int dpm_update(const DpmArgs& p, int rows, int C, hipStream_t s) {
+  const int64_t n = (int64_t)rows * C;
+  const bool vec = dpm_vec4_ok(p, C);
+  const dim3 grid((unsigned)cdiv64(vec ? n / 4 : n, 256));
+  if (vec)
+    hipLaunchKernelGGL(dpm4_kernel, grid, dim3(256), 0, s, p, rows, C);
+  else
+    hipLaunchKernelGGL(dpm_kernel, grid, dim3(256), 0, s, p, rows, C);
   SVC_LAUNCH_CHECK();
   return SVC_OK;
 }

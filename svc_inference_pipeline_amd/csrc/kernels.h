@@ -24,6 +24,7 @@ int content_map(const float* src, int B, int src_rows, int ld_src, int T, int D,
 int bucketize(const double* f0, const float* en, const float* mbins, const float* ebins, int nb, int* im, int* ie,
               int n, hipStream_t s);
 int plms_update(const PlmsArgs& p, int rows, int C, hipStream_t s);
+int dpm_update(const DpmArgs& p, int rows, int C, hipStream_t s);
 int ddpm_update(float* x, const float* eps, f16* x16, int ld16, int B, int T, int C, const DdpmArgs& a, hipStream_t s);
 int init_noise(float* x, f16* x16, int ld16, int B, int T, int C, uint64_t seed, const int* utt_ids, float std,
                hipStream_t s, bool bf);

@@ -329,6 +329,29 @@ svc_status svc_op_plms_update(const float* e0, const float* e1, const float* e2,
   return plms_update(p, rows, C, (hipStream_t)stream);
 }
 
+svc_status svc_op_dpm_update(float* x, const float* eps, const float* d_prev, float* d_out, int rows, int C, float sra,
+                             float srm1, float w0, float w1, float a, float b, int final_step, uint16_t* x16, int ld16,
+                             int bf16, void* stream) {
+  SVC_REQUIRE(x && eps && rows > 0 && C > 0 && (!x16 || ld16 >= C), "op_dpm_update: bad args");
+  SVC_REQUIRE((int64_t)rows * C <= INT32_MAX, "op_dpm_update: rows*C past 2^31");
+  DpmArgs p{};
+  p.x = x;
+  p.eps = eps;
+  p.d_prev = final_step ? nullptr : d_prev;
+  p.d_out = d_out;
+  p.sra = sra;
+  p.srm1 = srm1;
+  p.w0 = w0;
+  p.w1 = w1;
+  p.a = a;
+  p.b = b;
+  p.final_step = final_step != 0;
+  p.x16 = (f16*)x16;
+  p.ld16 = ld16;
+  p.bf16 = bf16 != 0;
+  return dpm_update(p, rows, C, (hipStream_t)stream);
+}
+
 svc_status svc_op_ddpm_update(float* x, const float* eps, int B, int T, int C, float sra, float srm1, float c1,
                               float c2, float sigma, const float* z, uint64_t seed, const int32_t* utt_ids, int step,
                               void* x16, int ld16, int bf16, void* stream) {

@@ -1,4 +1,4 @@
-// The DiffSVC denoiser and its DDPM / PLMS samplers.
+// The DiffSVC denoiser and its samplers: DDPM, PLMS, and DPM-Solver++(2M) / DDIM over a list of timesteps.
 #include <math.h>
 
 #include "engine.h"
@@ -138,10 +138,19 @@ int diffsvc_condproj(const PackedGemm& cp_all, const float* cond, f16* cond16, f
 
 }  // namespace svc
 
+// the sampler update that consumes a denoise's eps: none, the PLMS one or the DPM-Solver one
+struct EpsUpdate {
+  const PlmsArgs* plms = nullptr;
+  const DpmArgs* dpm = nullptr;
+  EpsUpdate() {}
+  EpsUpdate(const PlmsArgs* p) : plms(p) {}
+  EpsUpdate(const DpmArgs* d) : dpm(d) {}
+};
+
 // tv (device, optional): ragged batches, utterance b has tv[b] valid frames; only the dilated convs look across frames
-// plms (optional): the PLMS update that consumes this eps, launched right after the head
+// up (optional): the sampler update that consumes this eps, launched right after the head
 static int denoise(svc_ctx* c, const DenoiseBufs& bb, const f16* x16, int B, int T, int t, float* eps, hipStream_t s,
-                   const int* tv, const PlmsArgs* plms = nullptr) {
+                   const int* tv, EpsUpdate up = {}) {
   const int C = c->C, NL = c->n_layers, rows = B * T;
   const int ldx16 = (int)round_up(c->n_mel, 8);
   const float* dp = c->dproj + (size_t)t * NL * C;  // the step's diffusion projections, [NL][C]
@@ -161,7 +170,8 @@ static int denoise(svc_ctx* c, const DenoiseBufs& bb, const f16* x16, int B, int
   }
   if ((st = diffsvc_skipsum(c->skip_all, bb.g16, bb.g_ls, NL, bb.s16, C, c->head_split, rows, s))) return st;
   if ((st = diffsvc_head(c->skipproj, c->outproj, bb.s16, bb.u16, eps, C, c->n_mel, c->head_split, B, T, s))) return st;
-  return plms ? plms_update(*plms, rows, c->n_mel, s) : SVC_OK;
+  if (up.plms) return plms_update(*up.plms, rows, c->n_mel, s);
+  return up.dpm ? dpm_update(*up.dpm, rows, c->n_mel, s) : SVC_OK;
 }
 
 // the denoiser's part of a workspace layout (the sampler's, svc_diffsvc_eps's): gets only
@@ -201,16 +211,37 @@ int stage_frames(StageRing& ring, const int32_t* frames, int B, int T, hipStream
 // K (1..steps): the sampler starts at noise level K - 1, DDPM at step K - 1 and PLMS at ((K - 1) / interval) * interval
 // with an empty history; K = steps is the whole schedule (svc_diffsvc_sample). The start state is x_T when given, else
 // mel_src normalised and noised forward to level K - 1 (q_sample), else the x_T draw. noise (DDPM): [K][B*T][n_mel].
+// sol (optional; svc_diffsvc_sample_steps, which validates it): the solver loop over sol->ts instead, K = ts[0] + 1;
+// mode, interval and noise are not used then.
+struct SolverSteps {
+  const int32_t* ts;  // host, strictly decreasing, in [0, steps)
+  int n, order;
+};
+
+// The DPM-Solver++(2M) coefficients of the step t -> s < t (DpmArgs a, b; w0, w1 with the previous step's h_prev), in
+// f64 from the f32 alphas_cumprod table widened exactly, each rounded once: lambda = ln(ac / (1 - ac)) / 2,
+// h = lambda_s - lambda_t, a = sigma_s / sigma_t, b = -alpha_s expm1(-h), w1 = -h / (2 h_prev), w0 = 1 - w1.
+static double dpm_step_coeffs(const std::vector<float>& ac, int t, int s, double h_prev, DpmArgs& p) {
+  const double at = ac[t], as = ac[s];
+  const double h = 0.5 * log(as / (1.0 - as)) - 0.5 * log(at / (1.0 - at));
+  p.a = (float)sqrt((1.0 - as) / (1.0 - at));
+  p.b = (float)(-sqrt(as) * expm1(-h));
+  const double w1 = h_prev > 0.0 ? -h / (2.0 * h_prev) : 0.0;
+  p.w1 = (float)w1;
+  p.w0 = (float)(1.0 - w1);
+  return h;
+}
+
 static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* tv, int mode, int interval, int K,
                        const float* x_T, const float* mel_src, const float* noise, uint64_t seed,
-                       const int32_t* utt_ids, float* x0, hipStream_t stream) {
+                       const int32_t* utt_ids, float* x0, hipStream_t stream, const SolverSteps* sol = nullptr) {
   SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
   SVC_REQUIRE(K >= 1 && K <= c->steps, "sample: k_step %d outside [1, %d]", K, c->steps);
-  SVC_REQUIRE(mode == SVC_MODE_DDPM || (mode == SVC_MODE_PLMS && interval >= 1), "sample: mode %d interval %d", mode,
-              interval);
+  SVC_REQUIRE(sol || mode == SVC_MODE_DDPM || (mode == SVC_MODE_PLMS && interval >= 1), "sample: mode %d interval %d",
+              mode, interval);
   SVC_REQUIRE(x_T || utt_ids, "sample: need x_T or utt_ids for device noise");
   // DDPM draws step noise on the device unless `noise` is given; that noise is keyed by utterance id
-  SVC_REQUIRE(mode != SVC_MODE_DDPM || noise || utt_ids, "sample: DDPM without `noise` needs utt_ids");
+  SVC_REQUIRE(sol || mode != SVC_MODE_DDPM || noise || utt_ids, "sample: DDPM without `noise` needs utt_ids");
   hipStream_t s = (hipStream_t)stream;
   const int rows = B * T, nm = c->n_mel, ld16 = (int)round_up(nm, 8);
   DenoiseBufs bb;
@@ -276,6 +307,38 @@ static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* t
                        bb.lo16 + r * C, bb.cp_ls, bb.g_ls};
   };
 
+  if (sol) {
+    // Step j denoises at ts[j] and moves x to level ts[j + 1]: first order at j = 0 (no history yet), 2M from j = 1 when
+    // order is 2; the last call returns its data prediction (sigma_next = 0), where the 2M extrapolation has no finite h.
+    // One history buffer: D overwrites D_prev in place.
+    double h_prev = 0.0;
+    for (int j = 0; j < sol->n; ++j) {
+      const int t = sol->ts[j];
+      const bool last = j + 1 == sol->n;
+      DpmArgs p{};
+      p.sra = c->sra[t];
+      p.srm1 = c->srm1[t];
+      p.final_step = last;
+      p.ld16 = ld16;
+      p.bf16 = c->bf16;
+      const bool second = !last && sol->order == 2 && j > 0;
+      if (!last) h_prev = dpm_step_coeffs(c->alphas_cumprod_f32, t, sol->ts[j + 1], second ? h_prev : 0.0, p);
+      for (int h = 0; h < S; ++h) {
+        const Sub& u = sub[h];
+        const size_t r = u.r0;
+        DpmArgs q = p;
+        q.x = x + r * nm;
+        q.eps = eps + r * nm;
+        q.d_prev = second ? hist[0] + r * nm : nullptr;
+        q.d_out = sol->order == 2 && j + 2 < sol->n ? hist[0] + r * nm : nullptr;  // step j + 1 is a 2M step
+        q.x16 = last ? nullptr : x16 + r * ld16;
+        if ((st = denoise(c, sub_bufs(u), x16 + r * ld16, u.B, T, t, eps + r * nm, sb.stream(h),
+                          tv ? tv + u.b0 : nullptr, &q)))
+          return st;
+      }
+    }
+    return sb.join();
+  }
   if (mode == SVC_MODE_DDPM) {
     for (int i = K - 1; i >= 0; --i) {
       for (int h = 0; h < S; ++h) {
@@ -437,6 +500,32 @@ svc_status svc_diffsvc_sample_from(svc_ctx* c, const float* cond, int B, int T, 
   int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
   if (st ||
       (st = sample_impl(c, cond, B, T, tv, mode, interval, k_step, x_start, mel_src, noise, seed, utt_ids, x0, s)))
+    return st;
+  return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+}
+
+svc_status svc_diffsvc_sample_steps(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames,
+                                    const int32_t* timesteps, int n_steps, int order, const float* mel_src,
+                                    const float* x_start, uint64_t seed, const int32_t* utt_ids, float* x0,
+                                    void* stream) {
+  CTX_READY(c);
+  SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
+  SVC_REQUIRE(timesteps && n_steps >= 1, "sample_steps: empty timestep list");
+  SVC_REQUIRE(order == 1 || order == 2, "sample_steps: order %d (1: DDIM, 2: DPM-Solver++(2M))", order);
+  for (int j = 0; j < n_steps; ++j) {
+    SVC_REQUIRE(timesteps[j] >= 0 && timesteps[j] < c->steps, "sample_steps: timesteps[%d] = %d outside [0, %d)", j,
+                timesteps[j], c->steps);
+    SVC_REQUIRE(j == 0 || timesteps[j] < timesteps[j - 1], "sample_steps: timesteps not strictly decreasing at %d", j);
+  }
+  SVC_REQUIRE(!(mel_src && x_start), "sample_steps: give at most one of mel_src and x_start");
+  SVC_REQUIRE(x_start || utt_ids, "sample_steps: the device draw (x_start NULL) needs utt_ids");
+  hipStream_t s = (hipStream_t)stream;
+  const int* tv;
+  RingRetire retire_(c->lens_main, s);
+  const SolverSteps sol{timesteps, n_steps, order};
+  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
+  if (st || (st = sample_impl(c, cond, B, T, tv, SVC_MODE_PLMS, 1, timesteps[0] + 1, x_start, mel_src, nullptr, seed,
+                              utt_ids, x0, s, &sol)))
     return st;
   return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
 }

@@ -96,10 +96,11 @@ def resynth_files(engine, cfg, wav_paths):
 
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
                  f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                 loudness_mix=None):
+                 loudness_mix=None, solver=None, solver_steps=20):
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
     the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16). k_step, k_step_mel: shallow diffusion
-    and its start mel; loudness_mix: loudness envelope transfer (SVCPipeline.convert)."""
+    and its start mel; loudness_mix: loudness envelope transfer; solver, solver_steps: DPM-Solver++(2M) / DDIM instead of
+    DDPM / PLMS (SVCPipeline.convert)."""
     # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
     wav16f = None
     if wants_float16k(cfg):  # and utils/hubert.py:137-143's float 16 kHz copy from the same stage
@@ -117,13 +118,14 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
                                       pcm16=pcm16, key_shift=key_shift,
                                       **({} if k_step is None else dict(k_step=k_step)),
                                       **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
-                                      **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)))
+                                      **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
+                                      **({} if solver is None else dict(solver=solver, solver_steps=solver_steps)))
     return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
                   f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                  loudness_mix=None):
+                  loudness_mix=None, solver=None, solver_steps=20):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
     list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
     pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
@@ -140,7 +142,8 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
                                             fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16,
                                             key_shift=key_shift, **({} if k_step is None else dict(k_step=k_step)),
                                             **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
-                                            **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)))
+                                            **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
+                                            **({} if solver is None else dict(solver=solver, solver_steps=solver_steps)))
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
     return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
@@ -172,6 +175,13 @@ def build_parser():
                     help="with --k-step, the mel the sampler starts from: the source's own, or 'shifted': its "
                          "key-shifted mel, moved by the same factor as the F0 (singer median and --key), so that its "
                          "harmonics sit where the conditioner's pitch asks for them")
+    ap.add_argument("--solver", default=None, choices=sorted(C.SOLVERS),
+                    help="a multistep ODE solver instead of DDPM / PLMS: DPM-Solver++(2M) (dpmpp2m) or its first-order "
+                         "case DDIM (ddim), one denoiser call per step, from noise or with --k-step from the noised "
+                         "source mel (--fast and --speedup are then not used). Output quality at a given step count "
+                         "has been checked on an analytic denoiser and random weights only")
+    ap.add_argument("--solver-steps", type=int, default=20, metavar="N",
+                    help="with --solver, the number of timesteps, spaced evenly in log-SNR (default 20)")
     ap.add_argument("--loudness-mix", type=float, default=None, metavar="X",
                     help="loudness envelope transfer: the converted voice takes the source's slow RMS envelope; 0 "
                          "gives it the source's envelope, 1 leaves it unchanged (default: the step is not run)")
@@ -238,6 +248,11 @@ def main(argv=None):
         A.check_loudness_mix(args.loudness_mix)
     except ValueError as exc:
         ap.error(f"--loudness-mix: {exc}")
+    try:
+        if C.check_solver(args.solver, args.solver_steps) is not None:
+            C.solver_timesteps(cfg, args.k_step, args.solver_steps)
+    except ValueError as exc:
+        ap.error(f"--solver-steps: {exc}")
     print("Loading mapper and vocoder...", flush=True)
     hubert = args.hubert_ckpt or getattr(cfg, "contentVec_model", None)
     engine = build_engine(cfg, args.device, mapper, vocoder, args.whisper_ckpt, args.random_weights, args.seed,
@@ -259,11 +274,13 @@ def main(argv=None):
     if len(args.wav) == 1:
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
-                                k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix)]
+                                k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix, solver=args.solver,
+                                solver_steps=args.solver_steps)]
     else:
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
-                                k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix)
+                                k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix, solver=args.solver,
+                                solver_steps=args.solver_steps)
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
     for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU

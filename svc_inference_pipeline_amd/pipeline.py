@@ -29,6 +29,7 @@ from dataclasses import dataclass
 import torch
 
 from .audio import check_loudness_mix
+from .config import check_solver, solver_timesteps
 from .runtime import SVCEngine, check_k_step, check_k_step_mel, mel_frames
 
 WHISPER_WINDOW = 478720       # 16 kHz samples per long-input window (29.92 s)
@@ -218,7 +219,7 @@ class SVCPipeline:
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
                 noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                loudness_mix=None):
+                loudness_mix=None, solver=None, solver_steps=20, solver_spacing="logsnr"):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
         Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
         save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`.
@@ -231,20 +232,35 @@ class SVCPipeline:
         sit at the pitch the conditioner asks for. ConvertResult.mel stays the unshifted source mel.
         loudness_mix (None: the stage is not run, the call as before): loudness envelope transfer between the vocoder
         and the sample conversion (SVCEngine.loudness_match against wav24, in place): 0 gives the converted voice the
-        source's slow RMS envelope, 1 leaves it as it is; `wav` and `pcm` are the adjusted ones."""
+        source's slow RMS envelope, 1 leaves it as it is; `wav` and `pcm` are the adjusted ones.
+        solver, solver_steps, solver_spacing (solver None: the DDPM / PLMS sampler, the call as before): "dpmpp2m" or
+        "ddim" over solver_steps timesteps instead (SVCEngine.diffsvc_sample(solver=)), from noise or, with k_step, from
+        the noised source mel; fast_inference and speedup are not used then, and `noise` is a ValueError."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
+        solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
-                                 wav16_float, pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix)
+                                 wav16_float, pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix,
+                                 solver_kw)
+
+    def _solver_kw(self, solver, solver_steps, solver_spacing, k_step):
+        """The solver keywords validated (ValueError before any device work: the names, and the timestep list where the
+        engine's configuration has a schedule) -> the keywords for the calls below, none when solver is None."""
+        if check_solver(solver, solver_steps, solver_spacing) is None:
+            return {}
+        cfg = getattr(self.engine, "cfg", None)
+        if getattr(cfg, "mapper", None) is not None:
+            solver_timesteps(cfg, k_step, solver_steps, solver_spacing)
+        return dict(solver=solver, solver_steps=solver_steps, solver_spacing=solver_spacing)
 
     def _check_k_step(self, k_step):
         """k_step validated against the engine's schedule (ValueError before any device work); None stays None."""
         return None if k_step is None else check_k_step(k_step, getattr(self.engine, "cfg", None))
 
     def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
-                 pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None):
+                 pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -273,10 +289,10 @@ class SVCPipeline:
             utt_ids = torch.arange(wav24.shape[0], device=wav24.device, dtype=torch.int32)
         if k_step is None:
             x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, x_T=x_T, noise=noise,
-                                  seed=seed, utt_ids=utt_ids)
+                                  seed=seed, utt_ids=utt_ids, **(solver_kw or {}))
         else:  # the start mel was computed on the side stream: joined and recorded for this one above
             x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, noise=noise, seed=seed,
-                                  utt_ids=utt_ids, k_step=k_step, mel_src=mel_src)
+                                  utt_ids=utt_ids, k_step=k_step, mel_src=mel_src, **(solver_kw or {}))
         wav = e.bigvgan(x0)
         if loudness_mix is not None:  # T * hop <= N: every clip's source covers its output
             e.loudness_match(wav, wav24, mix=loudness_mix, out=wav)
@@ -284,7 +300,7 @@ class SVCPipeline:
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
                      utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                     loudness_mix=None):
+                     loudness_mix=None, solver=None, solver_steps=20, solver_spacing="logsnr"):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -297,7 +313,8 @@ class SVCPipeline:
         (SVCEngine.pcm16 on the batch: each utterance scaled by its own peak).
         key_shift: semitones, a scalar or one per utterance (shift_f0).
         k_step, k_step_mel: shallow diffusion for the whole batch and its start mel, as in convert().
-        loudness_mix: loudness envelope transfer for the whole batch, as in convert() (both routes)."""
+        loudness_mix: loudness envelope transfer for the whole batch, as in convert() (both routes).
+        solver, solver_steps, solver_spacing: the sampler for the whole batch, as in convert() (both routes)."""
         k_step = self._check_k_step(k_step)
         shallow = {} if k_step is None else dict(k_step=k_step)  # and the other keywords that are left out when unset
         if check_k_step_mel(k_step_mel, k_step) != "source":
@@ -305,6 +322,7 @@ class SVCPipeline:
         loudness_mix = check_loudness_mix(loudness_mix)
         if loudness_mix is not None:
             shallow["loudness_mix"] = loudness_mix
+        shallow.update(self._solver_kw(solver, solver_steps, solver_spacing, k_step))
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
             raise ValueError("convert_many: wavs24, wavs16, singers (and wavs16_float) must have one entry per utterance")
@@ -398,7 +416,8 @@ class SVCPipeline:
         return out
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
-                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None):
+                       utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None,
+                       solver=None, solver_steps=20, solver_spacing="logsnr"):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
@@ -407,27 +426,31 @@ class SVCPipeline:
         convert(): each clip starts from its own mel (k_step_mel="shifted": its own key-shifted mel, by its own factor),
         noised with its own utterance id's draw. loudness_mix: loudness envelope transfer, as in convert(): each
         clip's T_b * hop output samples against its own 24 kHz source (svc_loudness_match with both length tables),
-        before the sample conversion."""
+        before the sample conversion. solver, solver_steps, solver_spacing: the sampler, as in convert()."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
+        solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                                        pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix)
+                                        pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix, solver_kw)
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
-                      float16k=None, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None):
+                      float16k=None, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None, solver=None,
+                      solver_steps=20, solver_spacing="logsnr"):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
         HuBERT / ContentVec reads them as `wavs16_float`, what utils/hubert.py:137-143 feeds it; None (default): when
         the configuration names a HuBERT content type (wants_float16k); False: HuBERT is fed Whisper's int16-grid rows.
         Without a HuBERT type and with None or False, load_batch is called without the keyword.
-        loudness_mix: as in convert_ragged(), against the 24 kHz rows the load stage wrote."""
+        loudness_mix: as in convert_ragged(), against the 24 kHz rows the load stage wrote.
+        solver, solver_steps, solver_spacing: the sampler, as in convert()."""
         from . import audio as A
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
+        solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
         if wants_float16k(self.engine.cfg) if float16k is None else float16k:
             wavs24, wavs16, wavs16_float = A.load_batch(sources, self.engine.cfg.fs, self.engine, float16k=True)
         else:
@@ -437,10 +460,10 @@ class SVCPipeline:
                                    speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift,
                                    **({} if k_step is None else dict(k_step=k_step)),
                                    **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
-                                   **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)))
+                                   **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)), **solver_kw)
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                        pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None):
+                        pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -470,7 +493,7 @@ class SVCPipeline:
         uid = torch.tensor(ids, device=dev, dtype=torch.int32)
         shallow = {} if k_step is None else dict(k_step=k_step, mel_src=mel_src)  # joined and recorded above
         x0 = e.diffsvc_sample(cond, fast_inference=fast_inference, speedup=speedup, seed=seed, utt_ids=uid, frames=T_b,
-                              **shallow)
+                              **shallow, **(solver_kw or {}))
         wav = e.bigvgan(x0, frames=T_b)
         hop = e.cfg.hop_length
         if loudness_mix is not None:

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from . import weights as W
-from .config import load_stats, noise_schedule
+from .config import SOLVERS, check_solver, load_stats, noise_schedule, solver_timesteps
 from .singers import SingerF0Table
 
 MODE_DDPM, MODE_PLMS = 0, 1
@@ -462,19 +462,33 @@ class SVCEngine:
         return out
 
     def diffsvc_sample(self, cond, fast_inference=False, speedup=10, x_T=None, noise=None, seed=0, utt_ids=None,
-                       frames=None, k_step=None, mel_src=None, x_start=None):
+                       frames=None, k_step=None, mel_src=None, x_start=None, solver=None, solver_steps=20,
+                       solver_spacing="logsnr"):
         """svc_model_inference (modules/diffsvcrepo_inference.py:154-240) -> normalised mel x_0 f32 [B, T, n_mel].
         frames (ragged batch, host ints [B]): utterance b's mel frames; its rows past them come back as zeros.
         k_step (shallow diffusion, Diff-SVC's k_step; None: the whole schedule from x_T, the call as before): start
         at noise level k_step - 1 from exactly one of mel_src (the source's un-normalised log-mel [B, T, n_mel]:
         normalised and noised forward on the device, keyed by utt_ids) and x_start (an already noised state); DDPM
-        `noise` is then [k_step, B*T*n_mel] (svc_diffsvc_sample_from)."""
+        `noise` is then [k_step, B*T*n_mel] (svc_diffsvc_sample_from).
+        solver (None: the DDPM / PLMS call as before): "dpmpp2m" (DPM-Solver++(2M)) or "ddim" (its first-order case)
+        over config.solver_timesteps(cfg, k_step, solver_steps, solver_spacing): one denoiser call per timestep
+        (svc_diffsvc_sample_steps); fast_inference and speedup are not used. It composes with k_step / mel_src /
+        x_start and frames; without k_step the start state is x_T when given, else the device draw. The solvers draw
+        nothing per step: `noise` with a solver is a ValueError. Output quality at a given solver_steps has been checked
+        on an analytic denoiser and random weights only."""
         B, T, _ = cond.shape
         k_step = check_k_step(k_step, self.cfg)
+        solver = check_solver(solver, solver_steps, solver_spacing)
         if k_step is None and (mel_src is not None or x_start is not None):
             raise ValueError("diffsvc_sample: mel_src / x_start need k_step")
         if k_step is not None and (x_T is not None or (mel_src is None) == (x_start is None)):
             raise ValueError("diffsvc_sample: k_step takes exactly one of mel_src and x_start (and no x_T)")
+        if solver is not None:
+            if noise is not None:
+                raise ValueError("diffsvc_sample: `noise` with a solver (the solvers draw nothing per step)")
+            ts = solver_timesteps(self.cfg, k_step, solver_steps, solver_spacing)
+            return self._diffsvc_sample_steps(cond, ts, SOLVERS[solver], x_T if k_step is None else x_start, mel_src,
+                                              seed, utt_ids, frames)
         x0 = torch.empty(B, T, self.cfg.mapper.n_mel, device=cond.device, dtype=torch.float32)
         if utt_ids is None and ((x_T is None and x_start is None) or (noise is None and not fast_inference)):
             # device noise (x_T, and DDPM's per-step z) is keyed by utterance id: default to batch positions
@@ -494,6 +508,21 @@ class SVCEngine:
                   _ptr(x_T.contiguous()) if x_T is not None else None,
                   _ptr(noise.contiguous()) if noise is not None else None, ctypes.c_uint64(seed), _ptr(uid),
                   _ptr(x0), _stream())
+        return x0
+
+    def _diffsvc_sample_steps(self, cond, ts, order, start, mel_src, seed, utt_ids, frames):
+        """svc_diffsvc_sample_steps over the timesteps ts from the state `start` at level ts[0], or from mel_src noised
+        to it, or from the device draw."""
+        B, T, _ = cond.shape
+        if utt_ids is None and start is None:  # the start state is drawn on the device: keyed by batch position
+            utt_ids = torch.arange(B, device=cond.device, dtype=torch.int32)
+        uid = utt_ids.to(torch.int32).contiguous() if utt_ids is not None else None
+        x0 = torch.empty(B, T, self.cfg.mapper.n_mel, device=cond.device, dtype=torch.float32)
+        _lib.call("svc_diffsvc_sample_steps", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32),
+                  (ctypes.c_int32 * len(ts))(*ts), len(ts), order,
+                  _ptr(mel_src.contiguous()) if mel_src is not None else None,
+                  _ptr(start.contiguous()) if start is not None else None, ctypes.c_uint64(seed), _ptr(uid), _ptr(x0),
+                  _stream())
         return x0
 
     def bigvgan(self, x0, return_mel=False, frames=None):

@@ -15,7 +15,8 @@ it (so padding stays bounded: the kernels skip the padded tail, but its rows sti
 carries an utterance id (given, or a running counter) that keys its device noise, so its waveform is bit-identical to
 converting that clip alone with the same id, whatever it was batched with (tests/test_gpu_ragged.py). A request may ask
 for shallow diffusion (`k_step`, and `k_step_mel` for its start mel); a batch is formed only from requests with the same
-`k_step` and `k_step_mel`. The same holds for `loudness_mix` (loudness envelope transfer against the request's own
+`k_step` and `k_step_mel`, and the same solver setting (`solver`, `solver_steps`, `solver_spacing`: the server's
+defaults or a request's own). The same holds for `loudness_mix` (loudness envelope transfer against the request's own
 24 kHz source).
 
 Streams: submit() records an event on the caller's current stream, and the worker's stream waits for it before it
@@ -38,6 +39,7 @@ import torch
 
 from . import _lib
 from . import audio as A
+from .config import check_solver, solver_timesteps
 from .pipeline import SVCPipeline, wants_float16k
 from .runtime import check_k_step, check_k_step_mel, mel_frames
 
@@ -60,12 +62,15 @@ class _Request:
     k_step: object = None   # shallow diffusion: the sampler starts from the clip's own mel at this step (None: full)
     k_step_mel: str = "source"  # that start mel: the clip's own ("source") or its key-shifted one ("shifted")
     loudness_mix: object = None  # loudness envelope transfer against the source (None: not run)
+    solver: object = None   # (solver, solver_steps, solver_spacing), or None: the server's DDPM / PLMS sampler
 
 
 class SVCServer:
     def __init__(self, pipeline: SVCPipeline, max_batch=32, max_wait_s=0.02, length_ratio=2.0, fast_inference=True,
-                 speedup=10, seed=0, pcm16=False):
-        """pcm16=True: each future resolves to save_audio's samples of its waveform, int16 [T * hop + 2 * (fs // 20)]
+                 speedup=10, seed=0, pcm16=False, solver=None, solver_steps=20, solver_spacing="logsnr"):
+        """solver, solver_steps, solver_spacing: the default sampler of the requests (SVCPipeline.convert(solver=)); a
+        request may override each in submit() / submit_file(), and a batch holds requests of one setting only.
+        pcm16=True: each future resolves to save_audio's samples of its waveform, int16 [T * hop + 2 * (fs // 20)]
         (convert_ragged(pcm16=True): half the bytes to copy back, no host normalisation), instead of the f32 waveform."""
         if max_batch < 1 or max_wait_s < 0 or length_ratio < 1.0:
             raise ValueError("SVCServer: max_batch >= 1, max_wait_s >= 0, length_ratio >= 1")
@@ -74,6 +79,8 @@ class SVCServer:
         self.max_wait_s = float(max_wait_s)
         self.length_ratio = float(length_ratio)
         self.kw = dict(fast_inference=fast_inference, speedup=speedup, seed=seed)
+        self._solver = (solver, solver_steps, solver_spacing)
+        self._solver_setting(None, None, None, None)  # ValueError here for bad defaults
         if pcm16:
             self.kw["pcm16"] = True
         cfg = pipeline.engine.cfg
@@ -89,8 +96,23 @@ class SVCServer:
         self._worker = threading.Thread(target=self._run, name="svc-server", daemon=True)
         self._worker.start()
 
+    def _solver_setting(self, solver, solver_steps, solver_spacing, k_step):
+        """A request's solver setting, each keyword None taking the server's default (solver "none": DDPM / PLMS on a
+        server whose default is a solver), validated on the caller's thread -> (solver, solver_steps, solver_spacing),
+        or None for no solver."""
+        solver = self._solver[0] if solver is None else solver
+        solver = None if solver == "none" else solver
+        steps = self._solver[1] if solver_steps is None else solver_steps
+        spacing = self._solver[2] if solver_spacing is None else solver_spacing
+        if check_solver(solver, steps, spacing) is None:
+            return None
+        cfg = self.pipeline.engine.cfg
+        if getattr(cfg, "mapper", None) is not None:
+            solver_timesteps(cfg, k_step, steps, spacing)
+        return (solver, steps, spacing)
+
     def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None, key_shift=0.0, k_step=None,
-               k_step_mel="source", loudness_mix=None) -> Future:
+               k_step_mel="source", loudness_mix=None, solver=None, solver_steps=None, solver_spacing=None) -> Future:
         """Queue one utterance (device tensors: 24 kHz f32 [N], 16 kHz [N16], optional float 16 kHz for
         ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True).
         key_shift: semitones for this request, on top of the shift to its singer's F0 median.
@@ -99,18 +121,21 @@ class SVCServer:
         k_step_mel: "source" or "shifted", shallow diffusion's start mel (SVCPipeline.convert(k_step_mel=)); a batch
         holds one value of it too.
         loudness_mix: loudness envelope transfer for this request (SVCPipeline.convert_ragged(loudness_mix=)); a batch
-        holds requests of one value only (None, the stage not run, is a value of its own)."""
+        holds requests of one value only (None, the stage not run, is a value of its own).
+        solver, solver_steps, solver_spacing: this request's sampler instead of the server's default, each None: the
+        server's (solver="none": DDPM / PLMS on a server whose default is a solver); a batch holds one setting only."""
         n = int(wav24.shape[-1])
         if n < 1 or int(wav16.shape[-1]) < 1:
             raise ValueError("SVCServer.submit: empty audio")
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = A.check_loudness_mix(loudness_mix)
+        sol = self._solver_setting(solver, solver_steps, solver_spacing, k_step)
         req = _Request(wav24=wav24.reshape(-1), wav16=wav16.reshape(-1), singer=int(singer),
                        utt_id=next(self._ids) if utt_id is None else int(utt_id),
                        wav16_float=None if wav16_float is None else wav16_float.reshape(-1),
                        frames=self._frames(n), t_submit=time.monotonic(), key_shift=float(key_shift), k_step=k_step,
-                       k_step_mel=k_step_mel, loudness_mix=loudness_mix)
+                       k_step_mel=k_step_mel, loudness_mix=loudness_mix, solver=sol)
         if wav24.is_cuda:
             req.stream = torch.cuda.current_stream(wav24.device)
             req.ready = torch.cuda.Event()
@@ -123,7 +148,7 @@ class SVCServer:
         return req.future
 
     def submit_file(self, src, singer, utt_id=None, key_shift=0.0, k_step=None, k_step_mel="source",
-                    loudness_mix=None) -> Future:
+                    loudness_mix=None, solver=None, solver_steps=None, solver_spacing=None) -> Future:
         """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
         the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
         the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
@@ -131,11 +156,13 @@ class SVCServer:
         When the configuration names a HuBERT / ContentVec content type the decode also gives the request its float
         16 kHz row (audio.load_contentvec_audio of the file), so for batching it counts as a request with `wav16_float`:
         it shares a batch with tensor requests that carry one, never with tensor requests that do not.
-        k_step, k_step_mel, loudness_mix: as in submit()."""
+        k_step, k_step_mel, loudness_mix, solver, solver_steps, solver_spacing: as in submit()."""
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = A.check_loudness_mix(loudness_mix)
+        sol = self._solver_setting(solver, solver_steps, solver_spacing, k_step)
         req = self._file_request(src, singer, utt_id)
+        req.solver = sol
         req.loudness_mix = loudness_mix
         req.key_shift = float(key_shift)
         req.k_step = k_step
@@ -190,7 +217,7 @@ class SVCServer:
     # ------------------------------------------------------------------ worker
     def _take_batch(self):
         """The oldest request plus the pending ones of compatible length (within length_ratio, same ContentVec input
-        form, same k_step, k_step_mel and loudness_mix), at most max_batch; called with the lock held."""
+        form, same k_step, k_step_mel, loudness_mix and solver setting), at most max_batch; called with the lock held."""
         head = self._pending[0]
         lo, hi = head.frames / self.length_ratio, head.frames * self.length_ratio
         batch = [head]
@@ -198,7 +225,8 @@ class SVCServer:
             if len(batch) == self.max_batch:
                 break
             if (lo <= r.frames <= hi and self._has_float(r) == self._has_float(head) and r.k_step == head.k_step
-                    and r.k_step_mel == head.k_step_mel and r.loudness_mix == head.loudness_mix):
+                    and r.k_step_mel == head.k_step_mel and r.loudness_mix == head.loudness_mix
+                    and r.solver == head.solver):
                 batch.append(r)
         taken = set(map(id, batch))
         self._pending = [r for r in self._pending if id(r) not in taken]
@@ -278,6 +306,8 @@ class SVCServer:
                 kw["k_step_mel"] = batch[0].k_step_mel
             if batch[0].loudness_mix is not None:
                 kw["loudness_mix"] = batch[0].loudness_mix
+            if batch[0].solver is not None:
+                kw.update(zip(("solver", "solver_steps", "solver_spacing"), batch[0].solver))
             wavs = self.pipeline.convert_ragged([r.wav24 for r in batch], [r.wav16 for r in batch],
                                                 [r.singer for r in batch], wavs16_float=w16f,
                                                 utt_ids=[r.utt_id for r in batch], **kw)
