@@ -34,6 +34,9 @@
  *                          itself is written on the host)
  *   svc_loudness_match  <- no counterpart in the reference: so-vits-svc's loudness envelope adjustment, between
  *                          svc_bigvgan and svc_pcm16 (the output takes the source's slow RMS envelope)
+ *   svc_content_retrieve <- no counterpart in the reference: RVC's feature index (index_rate), between the content
+ *                          stage and svc_condition (each content frame blended with its k nearest frames of the
+ *                          target singer's own recordings; svc_index_norms prepares an index)
  *
  * Conventions
  *   - Tensors are caller-owned DEVICE buffers, time-major: row = b*T + t, channels contiguous.
@@ -93,7 +96,9 @@ svc_status svc_ctx_destroy(svc_ctx* ctx);
    "tune.<name>" keys set a kernel switch of this context at any time (gemm_variant, gemm3_direct, whisper_streams,
    sampler_streams, vocoder_streams, diff_head, amp_maxc, amp_ups, res_proj, gate_ws; "tune.reset" restores the creation-time values). Defaults
    are the measured production kernels; at creation an SVC_<NAME> environment variable overrides each. ctx may be
-   NULL for "tune.*" keys: the switches of the op-level entry points (svc_op_*, svc_gemm_bench). */
+   NULL for "tune.*" keys: the switches of the op-level entry points (svc_op_*, svc_gemm_bench).
+   "tune.retrieve_splits" is set the same way. It selects no kernel: it is the number of index splits of
+   svc_content_retrieve's grid (0, the default: chosen from the call's shape), on which the result does not depend. */
 svc_status svc_ctx_set_config(svc_ctx* ctx, const char* key, double value);
 /* the value of a configuration key set on this context, or of a kernel switch ("tune.<name>"; ctx NULL: the
    op-level context's); a key that was never set is SVC_ERR_INVALID */
@@ -443,6 +448,56 @@ int64_t svc_loudness_frames(int64_t n_out, int hop);
 svc_status svc_loudness_match(svc_ctx* ctx, const float* wav, const float* src, int B, int64_t S, int64_t S_src,
                               const int64_t* utt_samples, const int64_t* src_samples, int window, int hop, double mix,
                               double floor_rms, double max_gain, float* out, double* gain_out, void* stream);
+
+/* Feature retrieval, part 1: the squared norms of an index. index16: binary16 [N] rows of ld >= D halves (a singer's
+   enrolled content frames). norms[j] = (float) sum_c (double)x[j][c]^2 over the row's D values in column order (every
+   square is exact in f64), f32 [N]. One launch, one thread per row. The context need not be finalized.
+   SVC_ERR_INVALID before any HIP call: null index16 or norms; N outside [1, 2^31); D not a multiple of 8 in [8, 2048];
+   ld < D; rows that do not start on 16-byte boundaries (ld % 8 != 0 or a misaligned pointer); a context with
+   "operands.bf16" (fp16 only). */
+svc_status svc_index_norms(svc_ctx* ctx, const void* index16, int64_t N, int D, int ld, float* norms, void* stream);
+
+/* Feature retrieval, part 2 (RVC's feature index, `index_rate`; opt-in, between the content stage and svc_condition):
+   every content frame is blended with the distance-weighted mean of its k nearest frames of the index.
+   content16: binary16 [B*T] rows of ld halves, of which the first D are the frame; index16 [N] rows of ld_index halves
+   and norms f32 [N] (svc_index_norms of it); out16: binary16 [B*T] rows of ld_out halves.
+   A row r = b*T + t takes part when t < frames[b] (host int32 [B], NULL: all T) and sel[b] != 0 (host int32 [B], NULL:
+   all). For such a row, with q its D halves:
+     s_j  = norms[j] - 2 * dot(q, x_j): the products of the f16 values accumulated in f32 on v_mfma_f32_16x16x32_f16 in
+            ascending K, the same for every row and index row wherever they sit in a tile;
+     the k_eff = min(k, N) smallest under the total order (s_j, j): s compared as f32, an equal s goes to the lower j.
+            The order is total, so the selected set and its order are unique: they do not depend on the tiling or on
+            the number of index splits ("tune.retrieve_splits": 0 chosen from B*T and N, else that many);
+     d2_i = max((float)|q|^2 + s_i, (float)dist_floor), |q|^2 an f32 sum in an order fixed by D;
+     w_i  = (1 / d2_i) / sum_i (1 / d2_i) in f32, the sum over ranks ascending;
+     y    = sum_i w_i * x_i by f32 fma in rank order;
+     out  = round16(rate * y + (1 - rate) * q), two f32 products and one add ((float)rate and (float)(1 - rate)).
+   rate = 0 copies q bit for bit (the blend is not formed). rate = 1 replaces the frame by y.
+   Rows that take no part: a row of a selected utterance past frames[b] is written as +0 in columns 0..D-1; the rows of
+   an unselected utterance are copied when out16 != content16 and not touched when out16 == content16. Columns at or
+   past D of out16 are never touched. A ragged batch's utterance is bit-identical to the same utterance alone.
+   idx_out (optional, device int32 [B*T][k]): the selected j in rank order, -1 past k_eff and on rows that take no
+   part. dist_out (optional, device f32 [B*T][k]): the clamped d2_i, 0 in the same places.
+   out16 may be content16 itself (the same pointer and ld_out == ld: the wave that writes a row has finished reading
+   it); any other overlap of out16 with content16, and any with index16 or norms, is an error.
+   Two launches: knn_topk (the distance GEMM with the selection as its epilogue: the B*T x N scores are never stored;
+   a grid of query tiles x index splits, each split leaving 8 candidates per row in the workspace) and retrieve_blend
+   (merges the splits by the same order, weights, gathers, blends, 16-byte stores). The candidates come from the
+   context's workspace arena (64 B x B*T x splits), so the call is ordered with the other stages that use it; frames and
+   sel go through a ring of this entry point's own. The context need not be finalized.
+   Measured on MI355X (tools/retrieve_bench.py, profiles/retrieve_bench.json; 32 x 937 rows, D = 1024, k = 8): 1.84 /
+   6.58 / 24.6 ms per call against an index of 16,384 / 65,536 / 262,144 rows (knn_topk at 553 / 617 / 648 TFLOP/s),
+   0.32 ms for one clip of 937 rows against 65,536; 2.0 / 2.0 / 1.7 / 2.5 times the f16 torch.matmul of the same
+   product alone and 0.27 / 0.33 / 0.34 / 0.46 of the library composition (matmul, topk, gather, blend).
+   SVC_ERR_INVALID before any HIP call: a null context, content16, index16, norms or out16; B or T < 1 (or B*T >=
+   2^31 - 128); k outside [1, 8]; D not a multiple of 8 in [8, 2048]; N outside [1, 2^31); ld, ld_index or ld_out < D,
+   or rows that do not start on 16-byte boundaries; rate outside [0, 1] or NaN; dist_floor not > 0 (as f32);
+   frames[b] outside [0, T]; a partial overlap of the buffers; a context with "operands.bf16" (fp16 only: the message
+   says so). Non-finite features are the caller's error and give undefined rows (never an access outside the buffers). */
+svc_status svc_content_retrieve(svc_ctx* ctx, const void* content16, int B, int T, const int32_t* frames,
+                                const int32_t* sel, int D, int ld, const void* index16, const float* norms, int64_t N,
+                                int ld_index, int k, double rate, double dist_floor, void* out16, int ld_out,
+                                int32_t* idx_out, float* dist_out, void* stream);
 
 /* ---------------- op-level entry points (used by the parity tests; weights are unpacked f32 device arrays) */
 /* y[B*T_out][Cout] = conv1d(x[B*T_in][Cin]) ; w [Cout][Cin][k] ; act 0 none / 1 gelu / 2 relu */

@@ -416,6 +416,8 @@ struct Tuning {
   int gate_ws = 1;          // DiffSVC dilated conv + gate: 1 the weight-stationary row stream (gate_ws.hip), 0 conv_gemm4
                             // (the A-stationary dlayer.hip of round 5, gate alone or the whole layer, measured no
                             // faster and was removed: DESIGN.md, r05k)
+  int retrieve_splits = 0;  // svc_content_retrieve's index splits: 0 chosen from M and N (retrieve.hip), else that many
+                            // (at most one per 128-row index tile, and 64); the result does not depend on it
   std::string site_variant;  // "site=variant,...": per-call-site GEMM kernel override (environment only, A/B runs)
   void from_env();
   bool set(const char* name, double v);  // false: unknown name ("reset" restores the creation-time values)

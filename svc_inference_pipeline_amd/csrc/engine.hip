@@ -77,7 +77,8 @@ static int* tuning_field(T& t, const char* name) {
               {"whisper_streams", &t.whisper_streams}, {"sampler_streams", &t.sampler_streams},
               {"vocoder_streams", &t.vocoder_streams}, {"diff_head", &t.diff_head},
               {"amp_maxc", &t.amp_maxc},               {"res_proj", &t.res_proj},
-              {"gate_ws", &t.gate_ws},                 {"amp_ups", &t.amp_ups}};
+              {"gate_ws", &t.gate_ws},                 {"amp_ups", &t.amp_ups},
+              {"retrieve_splits", &t.retrieve_splits}};
   for (auto& it : ints)
     if (strcmp(it.name, name) == 0) return it.v;
   return nullptr;
@@ -85,7 +86,7 @@ static int* tuning_field(T& t, const char* name) {
 
 void Tuning::from_env() {
   for (const char* name : {"gemm_variant", "gemm3_direct", "whisper_streams", "sampler_streams", "vocoder_streams",
-                           "diff_head", "amp_maxc", "res_proj", "gate_ws", "amp_ups"}) {
+                           "diff_head", "amp_maxc", "res_proj", "gate_ws", "amp_ups", "retrieve_splits"}) {
     std::string env = "SVC_";
     for (const char* q = name; *q; ++q) env += (char)toupper((unsigned char)*q);
     if (const char* v = getenv(env.c_str())) *tuning_field(*this, name) = atoi(v);
@@ -272,6 +273,7 @@ svc_status svc_ctx_destroy(svc_ctx* c) {
   c->lens_main.release();
   c->lens_pcm.release();
   c->lens_loud.release();
+  c->lens_retr.release();
   c->lens_load.release();
   delete c;
   return SVC_OK;

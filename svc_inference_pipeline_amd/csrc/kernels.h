@@ -102,6 +102,12 @@ size_t loudness_power_bytes(int B, int64_t K_max);
 int loudness_match(const float* wav, const float* src, int B, int64_t S, int64_t S_src, void* table, int64_t K_max,
                    int window, int hop, double mix, double floor_rms, double max_gain, float* out, double* gain_out,
                    int64_t K_out, hipStream_t s);
+// retrieve.hip: feature retrieval. table (device): int32 frames[B], then int32 sel[B]
+int index_norms(const f16* x, int64_t N, int D, int ld, float* norms, hipStream_t s);
+int retrieve_splits(int M, int64_t N);
+int content_retrieve(const f16* q, int B, int T, int D, int ld, const int* table, const f16* x, const float* norms,
+                     int N, int ld_index, int k, double rate, double dist_floor, f16* out, int ld_out, int* idx_out,
+                     float* dist_out, Arena& ws, hipStream_t s);
 int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
              const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
              float* y_src, int sr_mono, int64_t S_mono, float* y_mono, float* y_mono_float, bool ex, int32_t* info,

@@ -2,6 +2,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <cmath>
+
 #include "engine.h"
 
 extern "C" {
@@ -455,6 +457,72 @@ int svc_hubert_dims(svc_ctx* c, int* final_dim, int* embed_dim) {
   if (final_dim) *final_dim = c->hFinal;
   if (embed_dim) *embed_dim = c->hD;
   return SVC_OK;
+}
+
+// ---------------------------------------------------------------------------- feature retrieval
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+svc_status svc_index_norms(svc_ctx* c, const void* index16, int64_t N, int D, int ld, float* norms, void* stream) {
+  SVC_REQUIRE(c, "index_norms: null context");
+  SVC_REQUIRE(index16 && norms, "index_norms: null %s", index16 ? "norms" : "index16");
+  SVC_REQUIRE(N >= 1 && N < (1LL << 31), "index_norms: N=%lld (1 <= N < 2^31)", (long long)N);
+  SVC_REQUIRE(D >= 8 && D <= 2048 && D % 8 == 0, "index_norms: D=%d (a multiple of 8 in [8, 2048])", D);
+  SVC_REQUIRE(ld >= D, "index_norms: ld=%d < D=%d", ld, D);
+  SVC_REQUIRE(ld % 8 == 0 && aligned16(index16), "index_norms: index16 rows must start on 16-byte boundaries (ld=%d)",
+              ld);
+  SVC_REQUIRE(!c->bf16 && cfgv(c, "operands.bf16", 0) == 0, "index_norms: fp16 only (this context has operands.bf16)");
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  return index_norms((const f16*)index16, N, D, ld, norms, (hipStream_t)stream);
+}
+
+svc_status svc_content_retrieve(svc_ctx* c, const void* content16, int B, int T, const int32_t* frames,
+                                const int32_t* sel, int D, int ld, const void* index16, const float* norms, int64_t N,
+                                int ld_index, int k, double rate, double dist_floor, void* out16, int ld_out,
+                                int32_t* idx_out, float* dist_out, void* stream) {
+  SVC_REQUIRE(c, "content_retrieve: null context");
+  SVC_REQUIRE(content16 && index16 && norms && out16, "content_retrieve: null %s",
+              !content16 ? "content16" : !index16 ? "index16" : !norms ? "norms" : "out16");
+  SVC_REQUIRE(B >= 1 && T >= 1 && (int64_t)B * T < (1LL << 31) - 128, "content_retrieve: B=%d T=%d", B, T);
+  SVC_REQUIRE(k >= 1 && k <= 8, "content_retrieve: k=%d (1 <= k <= 8)", k);
+  SVC_REQUIRE(D >= 8 && D <= 2048 && D % 8 == 0, "content_retrieve: D=%d (a multiple of 8 in [8, 2048])", D);
+  SVC_REQUIRE(N >= 1 && N < (1LL << 31), "content_retrieve: N=%lld (1 <= N < 2^31)", (long long)N);
+  SVC_REQUIRE(ld >= D && ld_index >= D && ld_out >= D, "content_retrieve: ld=%d ld_index=%d ld_out=%d (D=%d)", ld,
+              ld_index, ld_out, D);
+  SVC_REQUIRE(ld % 8 == 0 && ld_index % 8 == 0 && ld_out % 8 == 0 && aligned16(content16) && aligned16(index16) &&
+                  aligned16(out16),
+              "content_retrieve: rows must start on 16-byte boundaries (ld=%d ld_index=%d ld_out=%d)", ld, ld_index,
+              ld_out);
+  SVC_REQUIRE(rate >= 0.0 && rate <= 1.0, "content_retrieve: rate %g (must lie in [0, 1])", rate);
+  SVC_REQUIRE(dist_floor > 0.0 && (float)dist_floor > 0.0f && std::isfinite(dist_floor),
+              "content_retrieve: dist_floor %g (must be positive)", dist_floor);
+  // one staged table (retrieve.hip): int32 frames[B], int32 sel[B]
+  std::vector<int32_t> tab((size_t)2 * B);
+  for (int b = 0; b < B; ++b) {
+    tab[b] = frames ? frames[b] : T;
+    tab[(size_t)B + b] = sel ? (sel[b] != 0 ? 1 : 0) : 1;
+    SVC_REQUIRE(tab[b] >= 0 && tab[b] <= T, "content_retrieve: utterance %d: %d frames (row length %d)", b, tab[b], T);
+  }
+  {  // out is content itself (same rows) or shares no byte with it; it shares none with the index or the norms
+    const uintptr_t rows = (uintptr_t)B * (uintptr_t)T;
+    const uintptr_t q0 = reinterpret_cast<uintptr_t>(content16), o0 = reinterpret_cast<uintptr_t>(out16);
+    const uintptr_t x0 = reinterpret_cast<uintptr_t>(index16), n0 = reinterpret_cast<uintptr_t>(norms);
+    const uintptr_t nq = ((rows - 1) * (uintptr_t)ld + D) * 2, no = ((rows - 1) * (uintptr_t)ld_out + D) * 2;
+    const uintptr_t nx = ((uintptr_t)(N - 1) * (uintptr_t)ld_index + D) * 2, nn = (uintptr_t)N * 4;
+    SVC_REQUIRE((o0 == q0 && ld_out == ld) || o0 + no <= q0 || q0 + nq <= o0,
+                "content_retrieve: out16 overlaps content16 without being content16");
+    SVC_REQUIRE(o0 + no <= x0 || x0 + nx <= o0, "content_retrieve: out16 overlaps index16");
+    SVC_REQUIRE(o0 + no <= n0 || n0 + nn <= o0, "content_retrieve: out16 overlaps norms");
+  }
+  SVC_REQUIRE(!c->bf16 && cfgv(c, "operands.bf16", 0) == 0,
+              "content_retrieve: fp16 only (this context has operands.bf16)");
+  TuningScope tuning_scope_(&c->tune);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  hipStream_t s = (hipStream_t)stream;
+  RingRetire retire_(c->lens_retr, s);
+  void* dev = nullptr;
+  if (int st = c->lens_retr.put(tab.data(), tab.size() * sizeof(int32_t), s, &dev)) return st;
+  return content_retrieve((const f16*)content16, B, T, D, ld, reinterpret_cast<const int*>(dev), (const f16*)index16,
+                          norms, (int)N, ld_index, k, rate, dist_floor, (f16*)out16, ld_out, idx_out, dist_out, c->ws, s);
 }
 
 // ---------------------------------------------------------------------------- conditioner

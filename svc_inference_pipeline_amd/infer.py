@@ -30,7 +30,7 @@ from . import config as C
 from . import weights as W
 from .pipeline import SVCPipeline, hubert_content_type, wants_float16k
 from .runtime import K_STEP_MELS, SVCEngine, check_k_step, check_k_step_mel, mel_frames
-from .singers import SingerF0Table
+from .singers import SingerF0Table, check_index_rate
 
 
 def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckpt=None, random_weights=None, seed=0,
@@ -96,11 +96,11 @@ def resynth_files(engine, cfg, wav_paths):
 
 def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
                  f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                 loudness_mix=None, solver=None, solver_steps=20):
+                 loudness_mix=None, solver=None, solver_steps=20, index_rate=None):
     """One file through the GPU path -> (f32 waveform [T*hop] before save_audio's normalisation, T); with pcm16=True
     the waveform is save_audio's int16 samples instead (converted on the GPU, svc_pcm16). k_step, k_step_mel: shallow diffusion
     and its start mel; loudness_mix: loudness envelope transfer; solver, solver_steps: DPM-Solver++(2M) / DDIM instead of
-    DDPM / PLMS (SVCPipeline.convert)."""
+    DDPM / PLMS; index_rate: feature retrieval against the singer's enrolled index (SVCPipeline.convert)."""
     # utils/audio.py:10-55 and whisper_extractor/audio.py:22-49 in one device stage (raises on non-finite samples)
     wav16f = None
     if wants_float16k(cfg):  # and utils/hubert.py:137-143's float 16 kHz copy from the same stage
@@ -119,13 +119,14 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
                                       **({} if k_step is None else dict(k_step=k_step)),
                                       **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
                                       **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
+                                      **({} if index_rate is None else dict(index_rate=index_rate)),
                                       **({} if solver is None else dict(solver=solver, solver_steps=solver_steps)))
     return (res.pcm if pcm16 else res.wav)[0].cpu().numpy(), res.mel.shape[1]
 
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
                   f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                  loudness_mix=None, solver=None, solver_steps=20):
+                  loudness_mix=None, solver=None, solver_steps=20, index_rate=None):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
     list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
     pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
@@ -143,6 +144,7 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
                                             key_shift=key_shift, **({} if k_step is None else dict(k_step=k_step)),
                                             **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
                                             **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
+                                            **({} if index_rate is None else dict(index_rate=index_rate)),
                                             **({} if solver is None else dict(solver=solver, solver_steps=solver_steps)))
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
@@ -185,6 +187,16 @@ def build_parser():
     ap.add_argument("--loudness-mix", type=float, default=None, metavar="X",
                     help="loudness envelope transfer: the converted voice takes the source's slow RMS envelope; 0 "
                          "gives it the source's envelope, 1 leaves it unchanged (default: the step is not run)")
+    ap.add_argument("--index", action="store_true",
+                    help="with --enroll: also build the singer's retrieval index from the content frames of the "
+                         "recordings (needs --singer-index to keep it)")
+    ap.add_argument("--singer-index", default=None, metavar="FILE",
+                    help="per-singer retrieval indexes (.npz, singers.SingerIndexTable): loaded when the file exists, "
+                         "and saved after --enroll --index")
+    ap.add_argument("--index-rate", type=float, default=None, metavar="X",
+                    help="feature retrieval (RVC's index_rate): each content frame becomes X * (the weighted mean of "
+                         "its nearest frames of the singer's enrolled index) + (1 - X) * itself; 0..1 (default: the "
+                         "step is not run). Audible benefit is unverified: no trained checkpoint has been run with it")
     ap.add_argument("--resynth", action="store_true",
                     help="copy-synthesis: each file's own mel through the vocoder alone (judges a vocoder checkpoint; "
                          "needs no mapper or content checkpoint); output gen/<wav stem>_resynth.wav")
@@ -202,15 +214,19 @@ def build_parser():
     return ap
 
 
-def enroll_singer(engine, cfg, singer_name, wav_paths, f0_method="parselmouth", table_path=None):
+def enroll_singer(engine, cfg, singer_name, wav_paths, f0_method="parselmouth", table_path=None, index=False,
+                  index_path=None):
     """--enroll: SVCPipeline.enroll of the named singer from wav files -> the table entry; the table is saved to
-    table_path where given."""
+    table_path where given. index: also the singer's retrieval index (--index), saved to index_path where given."""
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
-    entry = SVCPipeline(engine, f0_method=f0_method).enroll(int(singers[singer_name]), sources=list(wav_paths))
+    entry = SVCPipeline(engine, f0_method=f0_method).enroll(int(singers[singer_name]), sources=list(wav_paths),
+                                                            **(dict(index=True) if index else {}))
     if table_path:
         engine.singer_f0.save(table_path)
+    if index and index_path:
+        engine.singer_index.save(index_path)
     return entry
 
 
@@ -249,6 +265,12 @@ def main(argv=None):
     except ValueError as exc:
         ap.error(f"--loudness-mix: {exc}")
     try:
+        check_index_rate(args.index_rate)
+    except ValueError as exc:
+        ap.error(f"--index-rate: {exc}")
+    if args.index and not args.enroll:
+        ap.error("--index needs --enroll")
+    try:
         if C.check_solver(args.solver, args.solver_steps) is not None:
             C.solver_timesteps(cfg, args.k_step, args.solver_steps)
     except ValueError as exc:
@@ -259,8 +281,11 @@ def main(argv=None):
                           hubert_ckpt=hubert)
     if args.singer_f0 and os.path.exists(args.singer_f0):
         engine.singer_f0 = SingerF0Table.load(args.singer_f0)
+    if args.singer_index and os.path.exists(args.singer_index):
+        engine.load_singer_index(args.singer_index)
     if args.enroll:
-        ent = enroll_singer(engine, cfg, args.singer, args.enroll, args.f0_method, args.singer_f0)
+        ent = enroll_singer(engine, cfg, args.singer, args.enroll, args.f0_method, args.singer_f0, index=args.index,
+                            index_path=args.singer_index)
         print(f"Enrolled {args.singer}: voiced F0 median {ent['median']:.3f} Hz over {ent['voiced']} voiced of "
               f"{ent['frames']} frames, {ent['n_utts']} file(s)", flush=True)
         if not args.wav:
@@ -275,12 +300,12 @@ def main(argv=None):
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
                                 k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix, solver=args.solver,
-                                solver_steps=args.solver_steps)]
+                                solver_steps=args.solver_steps, index_rate=args.index_rate)]
     else:
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
                                 k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix, solver=args.solver,
-                                solver_steps=args.solver_steps)
+                                solver_steps=args.solver_steps, index_rate=args.index_rate)
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
     for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU

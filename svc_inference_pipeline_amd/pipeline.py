@@ -31,6 +31,7 @@ import torch
 from .audio import check_loudness_mix
 from .config import check_solver, solver_timesteps
 from .runtime import SVCEngine, check_k_step, check_k_step_mel, mel_frames
+from .singers import check_index_rate
 
 WHISPER_WINDOW = 478720       # 16 kHz samples per long-input window (29.92 s)
 WINDOW_MEL_FRAMES = 2805      # = 1496 encoder frames * 15 / 8
@@ -133,38 +134,101 @@ class SVCPipeline:
         scale = [2.0 ** (k / 12.0) for k in ks] if any(ks) else None
         return targets, scale
 
-    def enroll(self, singer, sources=None, wavs24=None, max_batch=16):
+    def _check_index_rate(self, index_rate):
+        """index_rate validated (ValueError before any device work); None stays None. bf16 content has no retrieval."""
+        index_rate = check_index_rate(index_rate)
+        if index_rate is not None and getattr(self.engine, "operands", "fp16") == "bf16":
+            raise ValueError("index_rate: feature retrieval takes fp16 content (this engine runs operands='bf16')")
+        return index_rate
+
+    def retrieve(self, content, singers, index_rate, frames=None):
+        """Feature retrieval on content f16 [B, T, D] in place: one engine.content_retrieve call per distinct singer of
+        the batch that has an index in engine.singer_index, `sel` marking that singer's clips; clips of singers
+        without an index are left alone, and with no enrolled singer in the batch nothing is launched."""
+        e = self.engine
+        table = getattr(e, "singer_index", None)
+        if index_rate is None or not table:
+            return content
+        ids = [int(s) for s in (singers.reshape(-1).tolist() if hasattr(singers, "tolist") else singers)]
+        if len(ids) != content.shape[0]:
+            raise ValueError(f"{len(ids)} singers for a batch of {content.shape[0]}")
+        for s in sorted(set(ids)):
+            entry = table.get(s)
+            if entry is None:
+                continue
+            if entry["rows"].shape[1] != content.shape[2]:
+                raise ValueError(f"singer {s}: index rows are {entry['rows'].shape[1]} wide, content is "
+                                 f"{content.shape[2]}")
+            sel = None if all(i == s for i in ids) else [1 if i == s else 0 for i in ids]
+            e.content_retrieve(content, entry["rows"], entry["norms"], frames=frames, sel=sel, rate=index_rate,
+                               out=content)
+        return content
+
+    def enroll(self, singer, sources=None, wavs24=None, max_batch=16, index=False, index_max_rows=None,
+               wavs16=None, wavs16_float=None):
         """Measure a singer's voiced F0 median from that singer's own recordings and record it as the singer's pitch
         target (utils/acoustic_feature_extraction.py:21-30 on the GPU): wav files (`sources`: paths, bytes or
         memoryviews, decoded by audio.load_batch) or 24 kHz f32 device tensors (`wavs24`), in ragged chunks of at most
         max_batch clips through the configured F0 extractor; each clip's own frames are gathered into one flat buffer
         and ONE svc_f0_voiced_median call takes the median of its voiced cells. -> the table entry {median, voiced,
-        frames, n_utts} now in engine.singer_f0. A singer without a voiced frame is a ValueError; nothing is stored."""
+        frames, n_utts} now in engine.singer_f0. A singer without a voiced frame is a ValueError; nothing is stored.
+        index=True: the same recordings, in the same chunks, also go through the content stage (ragged_content), and
+        each clip's own T_b content rows are concatenated into the singer's retrieval index in engine.singer_index
+        (rows, their svc_index_norms, n_utts, frames, content types), which `index_rate=` on the conversion entry points
+        searches. With `wavs24` the 16 kHz copies are needed too: `wavs16` (and `wavs16_float` for ContentVec), as
+        convert_ragged takes them; `sources` are decoded to all of them. index_max_rows: an index of N > index_max_rows
+        rows keeps rows floor(i * N / index_max_rows), i < index_max_rows. The F0 entry is what it is without index."""
         e = self.engine
         if (sources is None) == (wavs24 is None):
             raise ValueError("enroll: give either sources (wav files) or wavs24 (24 kHz tensors)")
         if max_batch < 1:
             raise ValueError("enroll: max_batch >= 1")
+        if index_max_rows is not None and int(index_max_rows) < 1:
+            raise ValueError("enroll: index_max_rows >= 1")
+        if index and getattr(e, "operands", "fp16") == "bf16":
+            raise ValueError("enroll: index=True takes fp16 content (this engine runs operands='bf16')")
+        if index and sources is None and wavs16 is None:
+            raise ValueError("enroll: index=True with wavs24 needs the 16 kHz copies too (wavs16)")
         with e.lock:
             if sources is not None:
                 from . import audio as A
-                wavs24 = A.load_batch(list(sources), e.cfg.fs, e)[0]
+                if index and wants_float16k(e.cfg):
+                    wavs24, wavs16, wavs16_float = A.load_batch(list(sources), e.cfg.fs, e, float16k=True)
+                else:
+                    loaded = A.load_batch(list(sources), e.cfg.fs, e)
+                    wavs24 = loaded[0]
+                    wavs16 = loaded[1] if index else None
             wavs24 = [w.reshape(-1) for w in wavs24]
             if not wavs24:
                 raise ValueError("enroll: no recordings")
-            rows = []
+            if index and (len(wavs16) != len(wavs24) or (wavs16_float is not None and len(wavs16_float) != len(wavs24))):
+                raise ValueError("enroll: wavs16 (and wavs16_float) need one entry per recording")
+            rows, crows = [], []
             for i in range(0, len(wavs24), int(max_batch)):
                 w24, n24 = self._pad_stack(wavs24[i:i + int(max_batch)])
                 T_b = [mel_frames(k, e.cfg.n_fft, e.cfg.hop_length) for k in n24]
                 f0 = self.extract_f0(w24, max(T_b), n_samples=n24, T_b=T_b)
                 rows += [f0[b, :tb] for b, tb in enumerate(T_b)]
+                if index:
+                    w16f = None if wavs16_float is None else list(wavs16_float[i:i + int(max_batch)])
+                    c = self.ragged_content(list(wavs16[i:i + int(max_batch)]), T_b, max(T_b), w16f)
+                    crows += [c[b, :tb] for b, tb in enumerate(T_b)]
             flat = torch.cat(rows).to(torch.float64).contiguous()
             med, cnt = e.f0_voiced_median(flat)
             voiced = int(cnt.item())
             if voiced == 0:
                 raise ValueError(f"enroll: singer {singer}: no voiced frame in {len(wavs24)} recording(s)")
-            return e.singer_f0.set(singer, float(med.item()), voiced=voiced, frames=int(flat.numel()),
-                                   n_utts=len(wavs24))
+            entry = e.singer_f0.set(singer, float(med.item()), voiced=voiced, frames=int(flat.numel()),
+                                    n_utts=len(wavs24))
+            if index:
+                x = torch.cat(crows).contiguous()
+                N = x.shape[0]
+                if index_max_rows is not None and N > int(index_max_rows):
+                    keep = [i * N // int(index_max_rows) for i in range(int(index_max_rows))]
+                    x = x[torch.tensor(keep, device=x.device)].contiguous()
+                e.singer_index.set(singer, x, e.index_norms(x), n_utts=len(wavs24), frames=N,
+                                   content_types=sorted(e.cfg.mapper.content_feature))
+            return entry
 
     def content(self, wav16, T, wav16_float=None):
         """Content features of every type in cfg.mapper.content_feature mapped to T mel frames -> [B, T, sum of
@@ -219,7 +283,7 @@ class SVCPipeline:
 
     def convert(self, wav24, wav16, singer, fast_inference=True, speedup=10, seed=0, utt_ids=None, x_T=None,
                 noise=None, f0=None, wav16_float=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                loudness_mix=None, solver=None, solver_steps=20, solver_spacing="logsnr"):
+                loudness_mix=None, solver=None, solver_steps=20, solver_spacing="logsnr", index_rate=None):
         """infer.py's sequence for B equal-length clips -> ConvertResult. `f0` (optional, f64 [B, T]) replaces the
         Praat extraction; it is pitch-shifted on a copy (the caller's tensor is not modified). pcm16: also run
         save_audio's sample conversion on the device (SVCEngine.pcm16, its defaults) and return it as `pcm`.
@@ -235,15 +299,20 @@ class SVCPipeline:
         source's slow RMS envelope, 1 leaves it as it is; `wav` and `pcm` are the adjusted ones.
         solver, solver_steps, solver_spacing (solver None: the DDPM / PLMS sampler, the call as before): "dpmpp2m" or
         "ddim" over solver_steps timesteps instead (SVCEngine.diffsvc_sample(solver=)), from noise or, with k_step, from
-        the noised source mel; fast_inference and speedup are not used then, and `noise` is a ValueError."""
+        the noised source mel; fast_inference and speedup are not used then, and `noise` is a ValueError.
+        index_rate (None: the stage is not run, the call as before): feature retrieval between the content stage and
+        the conditioner (retrieve(): SVCEngine.content_retrieve in place, once per enrolled singer of the batch): each
+        content frame becomes index_rate * (the weighted mean of its nearest frames of its singer's enrolled index) +
+        (1 - index_rate) * itself; clips of singers without an index (enroll(index=True)) are left alone."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
+        index_rate = self._check_index_rate(index_rate)
         solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
         with self.engine.lock:
             return self._convert(wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0,
                                  wav16_float, pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix,
-                                 solver_kw)
+                                 solver_kw, index_rate)
 
     def _solver_kw(self, solver, solver_steps, solver_spacing, k_step):
         """The solver keywords validated (ValueError before any device work: the names, and the timestep list where the
@@ -260,7 +329,8 @@ class SVCPipeline:
         return None if k_step is None else check_k_step(k_step, getattr(self.engine, "cfg", None))
 
     def _convert(self, wav24, wav16, singer, fast_inference, speedup, seed, utt_ids, x_T, noise, f0, wav16_float,
-                 pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None):
+                 pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None,
+                 index_rate=None):
         e = self.engine
         T = mel_frames(wav24.shape[1], e.cfg.n_fft, e.cfg.hop_length)  # utils/mel.py:130-174 frame count
         # The 24 kHz features (mel / energy, and F0: Praat AC + pitch shift, latency-bound serial work on few CUs)
@@ -281,6 +351,8 @@ class SVCPipeline:
                 mel_src, info = e.mel_keyshift(wav24, factor)
         assert mel.shape[1] == T
         content = self.content(wav16, T, wav16_float)
+        if index_rate is not None:
+            content = self.retrieve(content, singer, index_rate)
         main.wait_stream(side)
         for t in (mel, energy, f0) + ((mel_src, factor, info) if shifted else ()):
             t.record_stream(main)
@@ -300,7 +372,7 @@ class SVCPipeline:
 
     def convert_many(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
                      utt_ids=None, bucketed=False, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                     loudness_mix=None, solver=None, solver_steps=20, solver_spacing="logsnr"):
+                     loudness_mix=None, solver=None, solver_steps=20, solver_spacing="logsnr", index_rate=None):
         """Ragged requests: lists of per-utterance device tensors (24 kHz f32 [N_i],
         16 kHz [N16_i], optional float 16 kHz for ContentVec) and singer ids -> list of waveforms f32 [T_i*hop] in
         input order, each bit-identical to converting that clip alone with the same utterance id
@@ -314,7 +386,8 @@ class SVCPipeline:
         key_shift: semitones, a scalar or one per utterance (shift_f0).
         k_step, k_step_mel: shallow diffusion for the whole batch and its start mel, as in convert().
         loudness_mix: loudness envelope transfer for the whole batch, as in convert() (both routes).
-        solver, solver_steps, solver_spacing: the sampler for the whole batch, as in convert() (both routes)."""
+        solver, solver_steps, solver_spacing: the sampler for the whole batch, as in convert() (both routes).
+        index_rate: feature retrieval for the whole batch, as in convert() (both routes)."""
         k_step = self._check_k_step(k_step)
         shallow = {} if k_step is None else dict(k_step=k_step)  # and the other keywords that are left out when unset
         if check_k_step_mel(k_step_mel, k_step) != "source":
@@ -322,6 +395,9 @@ class SVCPipeline:
         loudness_mix = check_loudness_mix(loudness_mix)
         if loudness_mix is not None:
             shallow["loudness_mix"] = loudness_mix
+        index_rate = self._check_index_rate(index_rate)
+        if index_rate is not None:
+            shallow["index_rate"] = index_rate
         shallow.update(self._solver_kw(solver, solver_steps, solver_spacing, k_step))
         n = len(wavs24)
         if not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
@@ -417,7 +493,7 @@ class SVCPipeline:
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
                        utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None,
-                       solver=None, solver_steps=20, solver_spacing="logsnr"):
+                       solver=None, solver_steps=20, solver_spacing="logsnr", index_rate=None):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
@@ -426,18 +502,22 @@ class SVCPipeline:
         convert(): each clip starts from its own mel (k_step_mel="shifted": its own key-shifted mel, by its own factor),
         noised with its own utterance id's draw. loudness_mix: loudness envelope transfer, as in convert(): each
         clip's T_b * hop output samples against its own 24 kHz source (svc_loudness_match with both length tables),
-        before the sample conversion. solver, solver_steps, solver_spacing: the sampler, as in convert()."""
+        before the sample conversion. solver, solver_steps, solver_spacing: the sampler, as in convert().
+        index_rate: feature retrieval, as in convert(): each clip's own T_b content rows against its own singer's
+        index (one svc_content_retrieve call per enrolled singer of the batch, `sel` marking that singer's clips)."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
+        index_rate = self._check_index_rate(index_rate)
         solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                                        pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix, solver_kw)
+                                        pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix, solver_kw,
+                                        index_rate)
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
                       float16k=None, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None, solver=None,
-                      solver_steps=20, solver_spacing="logsnr"):
+                      solver_steps=20, solver_spacing="logsnr", index_rate=None):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
@@ -445,11 +525,12 @@ class SVCPipeline:
         the configuration names a HuBERT content type (wants_float16k); False: HuBERT is fed Whisper's int16-grid rows.
         Without a HuBERT type and with None or False, load_batch is called without the keyword.
         loudness_mix: as in convert_ragged(), against the 24 kHz rows the load stage wrote.
-        solver, solver_steps, solver_spacing: the sampler, as in convert()."""
+        solver, solver_steps, solver_spacing: the sampler, as in convert(). index_rate: as in convert_ragged()."""
         from . import audio as A
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
+        index_rate = self._check_index_rate(index_rate)
         solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
         if wants_float16k(self.engine.cfg) if float16k is None else float16k:
             wavs24, wavs16, wavs16_float = A.load_batch(sources, self.engine.cfg.fs, self.engine, float16k=True)
@@ -460,10 +541,12 @@ class SVCPipeline:
                                    speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift,
                                    **({} if k_step is None else dict(k_step=k_step)),
                                    **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
-                                   **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)), **solver_kw)
+                                   **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
+                                   **({} if index_rate is None else dict(index_rate=index_rate)), **solver_kw)
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
-                        pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None):
+                        pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None,
+                        index_rate=None):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -484,6 +567,8 @@ class SVCPipeline:
             if shifted:
                 mel_src, info = e.mel_keyshift(w24, factor, n_samples=n24)
         content = self.ragged_content(list(wavs16), T_b, T, wavs16_float)
+        if index_rate is not None:
+            content = self.retrieve(content, [int(s) for s in singers], index_rate, frames=T_b)
         main.wait_stream(side)
         for t in (mel, energy, f0) + ((mel_src, factor, info) if shifted else ()):
             if t.is_cuda:

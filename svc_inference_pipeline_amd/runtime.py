@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from . import weights as W
 from .config import SOLVERS, check_solver, load_stats, noise_schedule, solver_timesteps
-from .singers import SingerF0Table
+from .singers import SingerF0Table, SingerIndexTable, check_index_rate, content_signature
 
 MODE_DDPM, MODE_PLMS = 0, 1
 
@@ -157,6 +157,9 @@ class SVCEngine:
         # per-singer F0 targets (SVCPipeline.enroll fills it); empty: every singer takes target_f0_median
         path = getattr(cfg, "singer_f0_file", None)
         self.singer_f0 = SingerF0Table.load(path) if path and os.path.exists(path) else SingerF0Table()
+        # per-singer retrieval indexes (SVCPipeline.enroll(index=True) or load_singer_index fill it); empty: index_rate
+        # finds no enrolled singer and launches nothing
+        self.singer_index = SingerIndexTable()
         self._ctx = ctypes.c_void_p()
         torch.cuda.set_device(device)
         _lib.call("svc_ctx_create", device, ctypes.byref(self._ctx))
@@ -621,3 +624,63 @@ class SVCEngine:
                   hop, mix, float(floor_rms), 0.0 if max_gain is None else float(max_gain), _ptr(out), _ptr(gain),
                   _stream())
         return (out, gain) if return_gain else out
+
+    def index_norms(self, x16):
+        """The squared norms of a retrieval index (svc_index_norms): x16 f16 [N, D] (rows may be a column slice of a
+        wider buffer: stride(0) >= D, a multiple of 8) -> f32 [N], each row's f64 sum of squares rounded to f32."""
+        if x16.dim() != 2 or x16.dtype != torch.float16 or x16.stride(1) != 1:
+            raise ValueError("index_norms: the index must be f16 [N, D] with contiguous rows")
+        N, D = x16.shape
+        norms = torch.empty(N, device=x16.device, dtype=torch.float32)
+        _lib.call("svc_index_norms", self._ctx, ctypes.c_void_p(x16.data_ptr()), N, D, x16.stride(0), _ptr(norms),
+                  _stream())
+        return norms
+
+    def content_retrieve(self, content, index, norms, frames=None, sel=None, k=8, rate=1.0, dist_floor=None, out=None,
+                         return_neighbours=False):
+        """Feature retrieval (svc_content_retrieve; RVC's index_rate): every frame of content f16 [B, T, D] that takes
+        part is replaced by rate * (the inverse-squared-distance weighted mean of its k nearest rows of index f16
+        [N, D]) + (1 - rate) * itself. norms: index_norms(index). frames (host ints [B]): utterance b has frames[b]
+        rows, the rows past them come back as zeros; sel (host 0 / 1 [B]): utterances with 0 take no part (copied, or
+        left alone in place). dist_floor: the clamp on a squared distance, None: 1e-4 * D. out: the result's tensor,
+        which may be content itself (in place); content, index and out may be column slices of wider buffers.
+        return_neighbours: also (idx int32 [B, T, k], d2 f32 [B, T, k]): the selected index rows in rank order and
+        their clamped squared distances, -1 / 0 past min(k, N) and on rows that take no part."""
+        if self.operands != "fp16":
+            raise ValueError("content_retrieve: fp16 content only (this engine runs operands='bf16')")
+        if content.dim() != 3 or content.dtype != torch.float16 or content.stride(2) != 1:
+            raise ValueError("content_retrieve: content must be f16 [B, T, D]")
+        B, T, D = content.shape
+        if content.stride(0) != T * content.stride(1):
+            raise ValueError("content_retrieve: content rows must keep one stride over the batch")
+        if index.dim() != 2 or index.dtype != torch.float16 or index.shape[1] != D or index.stride(1) != 1:
+            raise ValueError(f"content_retrieve: the index must be f16 [N, {D}]")
+        N = index.shape[0]
+        if norms.dtype != torch.float32 or norms.numel() != N:
+            raise ValueError(f"content_retrieve: norms must be f32 [{N}]")
+        rate = check_index_rate(rate)
+        if rate is None:
+            raise ValueError("content_retrieve: rate is None")
+        if out is None:
+            out = torch.empty(B, T, D, device=content.device, dtype=torch.float16)
+        elif (out.shape != content.shape or out.dtype != torch.float16 or out.stride(2) != 1
+              or out.stride(0) != T * out.stride(1)):
+            raise ValueError("content_retrieve: out must be f16 with content's shape")
+        idx = d2 = None
+        if return_neighbours:
+            idx = torch.empty(B, T, int(k), device=content.device, dtype=torch.int32)
+            d2 = torch.empty(B, T, int(k), device=content.device, dtype=torch.float32)
+        _lib.call("svc_content_retrieve", self._ctx, ctypes.c_void_p(content.data_ptr()), B, T,
+                  _host_lengths(frames, B, ctypes.c_int32), _host_lengths(sel, B, ctypes.c_int32), D,
+                  content.stride(1), ctypes.c_void_p(index.data_ptr()), _ptr(norms), N, index.stride(0), int(k), rate,
+                  1e-4 * D if dist_floor is None else float(dist_floor), ctypes.c_void_p(out.data_ptr()),
+                  out.stride(1), _ptr(idx), _ptr(d2), _stream())
+        return (out, idx, d2) if return_neighbours else out
+
+    def load_singer_index(self, path):
+        """Replace engine.singer_index by the table saved at `path` (SingerIndexTable.save), on this engine's device;
+        an index whose row width or content types differ from this configuration's content is a ValueError."""
+        dim, types = content_signature(self.cfg)
+        self.singer_index = SingerIndexTable.load(path, torch.device("cuda", self.device), dim=dim,
+                                                  content_types=types)
+        return self.singer_index

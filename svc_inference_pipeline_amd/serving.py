@@ -42,6 +42,7 @@ from . import audio as A
 from .config import check_solver, solver_timesteps
 from .pipeline import SVCPipeline, wants_float16k
 from .runtime import check_k_step, check_k_step_mel, mel_frames
+from .singers import check_index_rate
 
 
 @dataclass
@@ -63,6 +64,7 @@ class _Request:
     k_step_mel: str = "source"  # that start mel: the clip's own ("source") or its key-shifted one ("shifted")
     loudness_mix: object = None  # loudness envelope transfer against the source (None: not run)
     solver: object = None   # (solver, solver_steps, solver_spacing), or None: the server's DDPM / PLMS sampler
+    index_rate: object = None  # feature retrieval against the singer's enrolled index (None: not run)
 
 
 class SVCServer:
@@ -111,8 +113,16 @@ class SVCServer:
             solver_timesteps(cfg, k_step, steps, spacing)
         return (solver, steps, spacing)
 
+    def _index_rate(self, index_rate):
+        """A request's index_rate validated on the caller's thread (SVCPipeline's rule: bf16 content has no retrieval)."""
+        index_rate = check_index_rate(index_rate)
+        if index_rate is not None and getattr(self.pipeline.engine, "operands", "fp16") == "bf16":
+            raise ValueError("index_rate: feature retrieval takes fp16 content (this engine runs operands='bf16')")
+        return index_rate
+
     def submit(self, wav24, wav16, singer, utt_id=None, wav16_float=None, key_shift=0.0, k_step=None,
-               k_step_mel="source", loudness_mix=None, solver=None, solver_steps=None, solver_spacing=None) -> Future:
+               k_step_mel="source", loudness_mix=None, solver=None, solver_steps=None, solver_spacing=None,
+               index_rate=None) -> Future:
         """Queue one utterance (device tensors: 24 kHz f32 [N], 16 kHz [N16], optional float 16 kHz for
         ContentVec) -> Future resolving to its waveform f32 [T * hop] (int16 PCM with the server's pcm16=True).
         key_shift: semitones for this request, on top of the shift to its singer's F0 median.
@@ -123,19 +133,22 @@ class SVCServer:
         loudness_mix: loudness envelope transfer for this request (SVCPipeline.convert_ragged(loudness_mix=)); a batch
         holds requests of one value only (None, the stage not run, is a value of its own).
         solver, solver_steps, solver_spacing: this request's sampler instead of the server's default, each None: the
-        server's (solver="none": DDPM / PLMS on a server whose default is a solver); a batch holds one setting only."""
+        server's (solver="none": DDPM / PLMS on a server whose default is a solver); a batch holds one setting only.
+        index_rate: feature retrieval for this request (SVCPipeline.convert_ragged(index_rate=)); a batch holds
+        requests of one value only (None, the stage not run, is a value of its own)."""
         n = int(wav24.shape[-1])
         if n < 1 or int(wav16.shape[-1]) < 1:
             raise ValueError("SVCServer.submit: empty audio")
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = A.check_loudness_mix(loudness_mix)
+        index_rate = self._index_rate(index_rate)
         sol = self._solver_setting(solver, solver_steps, solver_spacing, k_step)
         req = _Request(wav24=wav24.reshape(-1), wav16=wav16.reshape(-1), singer=int(singer),
                        utt_id=next(self._ids) if utt_id is None else int(utt_id),
                        wav16_float=None if wav16_float is None else wav16_float.reshape(-1),
                        frames=self._frames(n), t_submit=time.monotonic(), key_shift=float(key_shift), k_step=k_step,
-                       k_step_mel=k_step_mel, loudness_mix=loudness_mix, solver=sol)
+                       k_step_mel=k_step_mel, loudness_mix=loudness_mix, solver=sol, index_rate=index_rate)
         if wav24.is_cuda:
             req.stream = torch.cuda.current_stream(wav24.device)
             req.ready = torch.cuda.Event()
@@ -148,7 +161,7 @@ class SVCServer:
         return req.future
 
     def submit_file(self, src, singer, utt_id=None, key_shift=0.0, k_step=None, k_step_mel="source",
-                    loudness_mix=None, solver=None, solver_steps=None, solver_spacing=None) -> Future:
+                    loudness_mix=None, solver=None, solver_steps=None, solver_spacing=None, index_rate=None) -> Future:
         """Queue one wav file (a path, bytes or a memoryview) -> Future, as submit(). Only the header is parsed here:
         the request's frame count for batching follows from its length and rate (svc_resample_len, mel_frames), and
         the worker decodes all the file requests of a batch in one audio.load_batch (they may share a batch with tensor
@@ -156,13 +169,15 @@ class SVCServer:
         When the configuration names a HuBERT / ContentVec content type the decode also gives the request its float
         16 kHz row (audio.load_contentvec_audio of the file), so for batching it counts as a request with `wav16_float`:
         it shares a batch with tensor requests that carry one, never with tensor requests that do not.
-        k_step, k_step_mel, loudness_mix, solver, solver_steps, solver_spacing: as in submit()."""
+        k_step, k_step_mel, loudness_mix, solver, solver_steps, solver_spacing, index_rate: as in submit()."""
         k_step = check_k_step(k_step, self.pipeline.engine.cfg)  # ValueError here, not in the worker
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = A.check_loudness_mix(loudness_mix)
+        index_rate = self._index_rate(index_rate)
         sol = self._solver_setting(solver, solver_steps, solver_spacing, k_step)
         req = self._file_request(src, singer, utt_id)
         req.solver = sol
+        req.index_rate = index_rate
         req.loudness_mix = loudness_mix
         req.key_shift = float(key_shift)
         req.k_step = k_step
@@ -217,7 +232,7 @@ class SVCServer:
     # ------------------------------------------------------------------ worker
     def _take_batch(self):
         """The oldest request plus the pending ones of compatible length (within length_ratio, same ContentVec input
-        form, same k_step, k_step_mel, loudness_mix and solver setting), at most max_batch; called with the lock held."""
+        form, same k_step, k_step_mel, loudness_mix, index_rate and solver setting), at most max_batch; called with the lock held."""
         head = self._pending[0]
         lo, hi = head.frames / self.length_ratio, head.frames * self.length_ratio
         batch = [head]
@@ -226,7 +241,7 @@ class SVCServer:
                 break
             if (lo <= r.frames <= hi and self._has_float(r) == self._has_float(head) and r.k_step == head.k_step
                     and r.k_step_mel == head.k_step_mel and r.loudness_mix == head.loudness_mix
-                    and r.solver == head.solver):
+                    and r.solver == head.solver and r.index_rate == head.index_rate):
                 batch.append(r)
         taken = set(map(id, batch))
         self._pending = [r for r in self._pending if id(r) not in taken]
@@ -306,6 +321,8 @@ class SVCServer:
                 kw["k_step_mel"] = batch[0].k_step_mel
             if batch[0].loudness_mix is not None:
                 kw["loudness_mix"] = batch[0].loudness_mix
+            if batch[0].index_rate is not None:
+                kw["index_rate"] = batch[0].index_rate
             if batch[0].solver is not None:
                 kw.update(zip(("solver", "solver_steps", "solver_spacing"), batch[0].solver))
             wavs = self.pipeline.convert_ragged([r.wav24 for r in batch], [r.wav16 for r in batch],

@@ -7,6 +7,9 @@ the GPU (svc_f0_voiced_median) from the singer's own recordings; a singer withou
 """
 import json
 
+import numpy as np
+import torch
+
 
 class SingerF0Table:
     """singer id (int) -> {"median": float (Hz), "voiced": int, "frames": int, "n_utts": int}."""
@@ -64,4 +67,91 @@ class SingerF0Table:
             m = v["median"]
             t.set(int(k), float.fromhex(m) if isinstance(m, str) else float(m), v.get("voiced", 0), v.get("frames", 0),
                   v.get("n_utts", 0))
+        return t
+
+
+def check_index_rate(index_rate):
+    """Feature retrieval's blend rate as a float in [0, 1], else ValueError before any device work; None (the stage is
+    not run) stays None."""
+    if index_rate is None:
+        return None
+    ok = isinstance(index_rate, (int, float, np.integer, np.floating)) and not isinstance(index_rate, (bool, np.bool_))
+    if not ok or not (0.0 <= float(index_rate) <= 1.0):
+        raise ValueError(f"index_rate {index_rate!r}: a number in [0, 1] (None: no feature retrieval)")
+    return float(index_rate)
+
+
+def content_signature(cfg):
+    """(D, content types) of the content buffer the configuration's conditioner reads: the types of
+    cfg.mapper.content_feature in ascending name order and the sum of their widths (SVCPipeline.content)."""
+    m = cfg.mapper
+    types = sorted(m.content_feature)
+    return sum(int(m.input_content_dim[t]) for t in types), types
+
+
+class SingerIndexTable:
+    """singer id (int) -> a retrieval index: {"rows": f16 [N, D] tensor of the singer's enrolled content frames,
+    "norms": f32 [N] (svc_index_norms of the rows), "n_utts": int, "frames": int (content frames seen, before any
+    thinning), "content_types": list of str the rows were built from}. SVCPipeline.enroll(index=True) fills it;
+    svc_content_retrieve searches it (`index_rate=` on the conversion entry points)."""
+
+    def __init__(self):
+        self._e = {}
+
+    def set(self, singer, rows, norms, n_utts=0, frames=0, content_types=()):
+        if rows.dim() != 2 or rows.dtype != torch.float16 or rows.shape[0] < 1:
+            raise ValueError(f"singer {singer}: index rows must be f16 [N >= 1, D]")
+        if norms.dtype != torch.float32 or norms.shape != (rows.shape[0],):
+            raise ValueError(f"singer {singer}: norms must be f32 [{rows.shape[0]}]")
+        self._e[int(singer)] = dict(rows=rows.contiguous(), norms=norms.contiguous(), n_utts=int(n_utts),
+                                    frames=int(frames), content_types=[str(t) for t in content_types])
+        return self._e[int(singer)]
+
+    def get(self, singer, default=None):
+        return self._e.get(int(singer), default)
+
+    def __len__(self):
+        return len(self._e)
+
+    def __bool__(self):
+        return bool(self._e)
+
+    def __contains__(self, singer):
+        return int(singer) in self._e
+
+    def __iter__(self):
+        return iter(sorted(self._e))
+
+    def save(self, path):
+        """.npz: per singer the rows as uint16 bit patterns and the f32 norms, and one JSON document of the metadata."""
+        arrays, meta = {}, {}
+        for k, v in sorted(self._e.items()):
+            arrays[f"rows_{k}"] = v["rows"].detach().cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+            arrays[f"norms_{k}"] = v["norms"].detach().cpu().numpy()
+            meta[str(k)] = dict(n_utts=v["n_utts"], frames=v["frames"], content_types=v["content_types"],
+                                rows=int(v["rows"].shape[0]), dim=int(v["rows"].shape[1]))
+        with open(path, "wb") as f:
+            np.savez(f, meta=np.array(json.dumps({"singer_index": meta})), **arrays)
+
+    @classmethod
+    def load(cls, path, device="cpu", dim=None, content_types=None):
+        """dim / content_types (content_signature of the engine's configuration): an index whose row width or
+        content types differ is a ValueError: its frames come from another content space."""
+        t = cls()
+        with np.load(path, allow_pickle=False) as doc:
+            meta = json.loads(str(doc["meta"]))["singer_index"]
+            for k, m in meta.items():
+                rows = np.ascontiguousarray(doc[f"rows_{k}"])
+                if rows.dtype != np.uint16 or rows.ndim != 2 or rows.shape != (m["rows"], m["dim"]):
+                    raise ValueError(f"{path}: singer {k}: rows {rows.dtype} {rows.shape}, metadata says uint16 "
+                                     f"[{m['rows']}, {m['dim']}]")
+                if dim is not None and rows.shape[1] != int(dim):
+                    raise ValueError(f"{path}: singer {k}: index rows are {rows.shape[1]} wide, the configuration's "
+                                     f"content is {int(dim)}")
+                if content_types is not None and list(m["content_types"]) != [str(c) for c in content_types]:
+                    raise ValueError(f"{path}: singer {k}: index built from content types {m['content_types']}, the "
+                                     f"configuration uses {list(content_types)}")
+                t.set(int(k), torch.from_numpy(rows.view(np.int16)).view(torch.float16).to(device),
+                      torch.from_numpy(np.ascontiguousarray(doc[f"norms_{k}"], np.float32)).to(device), m["n_utts"],
+                      m["frames"], m["content_types"])
         return t
