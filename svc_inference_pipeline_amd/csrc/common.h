@@ -345,7 +345,7 @@ __device__ __forceinline__ void plms_math4(const PlmsArgs& p, const float4* ev, 
   x_out = make_float4(x.x + p.d * (p.A * x.x - p.Bc * e[0]), x.y + p.d * (p.A * x.y - p.Bc * e[1]),
                       x.z + p.d * (p.A * x.z - p.Bc * e[2]), x.w + p.d * (p.A * x.w - p.Bc * e[3]));
 }
-// One DDPM p_sample update (stage_diffsvc.hip sample_impl, elementwise.hip ddpm_update)
+// One DDPM p_sample update (stage_diffsvc.hip run_ddpm, elementwise.hip ddpm_update)
 struct DdpmArgs {
   float sra, srm1, c1, c2, sigma;  // sigma = exp(0.5*logvar) * (t > 0)
   const float* z; uint64_t seed; const int* utt_ids; int step;

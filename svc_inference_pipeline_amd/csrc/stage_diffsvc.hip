@@ -19,7 +19,6 @@ struct DenoiseBufs {
   f16* cond16;   // [rows][3C] the conditioner output as the [hi | lo | hi] operand of the projections (project_cond)
 };
 
-
 namespace svc {
 
 // Residual stream x in split-fp16 storage (x + dproj_l = hi + lo, ~22 significand bits in 4 bytes): the layer's GEMM
@@ -138,15 +137,16 @@ int diffsvc_condproj(const PackedGemm& cp_all, const float* cond, f16* cond16, f
 
 }  // namespace svc
 
-// the sampler update that consumes a denoise's eps: none, the PLMS one or the DPM-Solver one
+// The sampler update that denoise launches on its eps: the PLMS one (run_plms), the DPM-Solver one (run_solver), or
+// none (svc_diffsvc_eps; run_ddpm, whose update also draws and is launched by the loop itself).
 struct EpsUpdate {
   const PlmsArgs* plms = nullptr;
   const DpmArgs* dpm = nullptr;
-  EpsUpdate() {}
-  EpsUpdate(const PlmsArgs* p) : plms(p) {}
+  EpsUpdate(const PlmsArgs* p = nullptr) : plms(p) {}
   EpsUpdate(const DpmArgs* d) : dpm(d) {}
 };
 
+// eps = model(x16, t) for B utterances of T frames with the buffers bb, on s (the sampler: SamplerRun::denoise)
 // tv (device, optional): ragged batches, utterance b has tv[b] valid frames; only the dilated convs look across frames
 // up (optional): the sampler update that consumes this eps, launched right after the head
 static int denoise(svc_ctx* c, const DenoiseBufs& bb, const f16* x16, int B, int T, int t, float* eps, hipStream_t s,
@@ -208,15 +208,189 @@ int stage_frames(StageRing& ring, const int32_t* frames, int B, int T, hipStream
 
 }  // namespace svc
 
-// K (1..steps): the sampler starts at noise level K - 1, DDPM at step K - 1 and PLMS at ((K - 1) / interval) * interval
-// with an empty history; K = steps is the whole schedule (svc_diffsvc_sample). The start state is x_T when given, else
-// mel_src normalised and noised forward to level K - 1 (q_sample), else the x_T draw. noise (DDPM): [K][B*T][n_mel].
-// sol (optional; svc_diffsvc_sample_steps, which validates it): the solver loop over sol->ts instead, K = ts[0] + 1;
-// mode, interval and noise are not used then.
-struct SolverSteps {
-  const int32_t* ts;  // host, strictly decreasing, in [0, steps)
-  int n, order;
+// An entry point's work on a ragged batch: stage `frames`, run body(tv), and zero out's rows past each utterance's end,
+// which hold no result. The staged table is retired on every return path.
+template <class Body>
+static int with_frames(svc_ctx* c, const int32_t* frames, int B, int T, float* out, hipStream_t s, Body&& body) {
+  const int* tv;
+  RingRetire retire_(c->lens_main, s);
+  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
+  if (st || (st = body(tv))) return st;
+  return tv ? zero_tail_rows(out, B, T, c->n_mel, tv, s) : SVC_OK;
+}
+
+// ---------------------------------------------------------------------------- samplers
+// An entry point fills a SampleRequest; sample_impl validates it, plans the workspace and projects the conditioner
+// (SamplerRun), sets the start state (set_start) and runs the request's step loop (run_ddpm, run_plms, run_solver).
+enum SamplerKind { SAMPLER_DDPM, SAMPLER_PLMS, SAMPLER_SOLVER };
+struct SampleRequest {
+  // start: noise level K - 1, K in 1..steps (K = steps is the whole schedule, svc_diffsvc_sample). DDPM starts at step
+  // K - 1, PLMS at ((K - 1) / interval) * interval with an empty history, the solver at ts[0] = K - 1. The state is
+  // x_T when given, else mel_src normalised and noised forward to level K - 1 (q_sample), else the x_T draw.
+  int K;
+  const float *x_T, *mel_src;
+  uint64_t seed;  // noise keys of whatever is drawn on the device
+  const int32_t* utt_ids;
+  SamplerKind kind;    // sampler: the kind, then each kind's own arguments
+  int mode, interval;  // DDPM / PLMS: the caller's SVC_MODE_* word, which sample_impl validates, and PLMS's interval
+  const float* noise;  // DDPM, optional: [K][B*T][n_mel], else drawn on the device
+  const int32_t* ts;   // solver: n_ts host timesteps, strictly decreasing, in [0, steps); order 1 (DDIM) or 2 (2M)
+  int n_ts, order;     // (svc_diffsvc_sample_steps validates them)
+  // sample_impl rejects a mode that is neither
+  static SamplerKind of_mode(int mode) { return mode == SVC_MODE_DDPM ? SAMPLER_DDPM : SAMPLER_PLMS; }
 };
+
+// What every step loop needs of one sampler call: the shapes, the workspace and the walk over the sub-batches.
+struct SamplerRun {
+  svc_ctx* c;
+  int B, T;
+  const int* tv;
+  int rows, nm, ld16;  // B * T, n_mel, the row length of x16 / xp16 (n_mel rounded up to 8; the pad channels stay zero)
+  float *x, *eps, *hist[5], *xp;  // x: the sampler state, which lives in the output buffer
+  DenoiseBufs bb;
+  f16 *x16, *xp16;
+  SubBatches sb;  // sub-batch h: utterances sb.b0(h) .. sb.b0(h + 1) - 1 on sb.stream(h)
+
+  // One layout for every sampler: DDPM uses no hist, xp or xp16 and the solver only hist[0], but these gets, their
+  // sizes and their order are what svc_ctx_memory's workspace figure and the arena's sizing pass see. Shrinking the
+  // layout per sampler is a behaviour change for another day.
+  int plan() {
+    return c->ws.plan([&](Arena& ws) {
+      layout_denoise(c, ws, B, T, bb);
+      x16 = ws.get<f16>((size_t)rows * ld16);
+      eps = ws.get<float>((size_t)rows * nm);
+      for (int k = 0; k < 5; ++k) hist[k] = ws.get<float>((size_t)rows * nm);
+      xp = ws.get<float>((size_t)rows * nm);
+      xp16 = ws.get<f16>((size_t)rows * ld16);
+    });
+  }
+  // sub-batch h's rows of a whole-batch [rows][nm] f32 or [rows][ld16] 16-bit buffer
+  template <class F>
+  F* rowsf(F* p, int h) const { return p + (size_t)sb.b0(h) * T * nm; }
+  f16* rows16(f16* p, int h) const { return p + (size_t)sb.b0(h) * T * ld16; }
+  // the denoiser on sub-batch h and its stream: eps_out = model(x16_in, t), both whole-batch buffers, then the update
+  int denoise(int h, f16* x16_in, int t, float* eps_out, EpsUpdate up = {}) {
+    const size_t r = (size_t)sb.b0(h) * T, C = c->C;
+    const DenoiseBufs ub{bb.cp16 + r * 2 * C, bb.y16 + r * C, bb.g16 + r * C, bb.s16 + r * 3 * C, bb.u16 + r * 3 * C,
+                         bb.lo16 + r * C, bb.cp_ls, bb.g_ls};
+    return ::denoise(c, ub, rows16(x16_in, h), sb.b0(h + 1) - sb.b0(h), T, t, rowsf(eps_out, h), sb.stream(h),
+                     tv ? tv + sb.b0(h) : nullptr, up);
+  }
+};
+
+// The start state into x and its 16-bit copy x16, with the pad channels of x16 and xp16 zeroed around it
+static int set_start(SamplerRun& r, const SampleRequest& q, hipStream_t s) {
+  SVC_HIP_CHECK(hipMemsetAsync(r.x16, 0, (size_t)r.rows * r.ld16 * sizeof(f16), s));  // zero pad channels
+  if (q.x_T) {
+    SVC_HIP_CHECK(hipMemcpyAsync(r.x, q.x_T, (size_t)r.rows * r.nm * 4, hipMemcpyDeviceToDevice, s));
+    if (int st = f32_to_f16(r.x, r.nm, r.x16, r.ld16, r.rows, r.nm, r.ld16, s, r.c->bf16)) return st;
+  } else if (q.mel_src) {
+    const float ac = r.c->alphas_cumprod_f32[q.K - 1];
+    QSampleArgs a{};
+    a.mel = q.mel_src;
+    a.mn = r.c->mel_min;
+    a.mx = r.c->mel_max;
+    a.noised = 1;
+    a.a = sqrtf(ac);
+    a.b = sqrtf(1.0f - ac);
+    a.seed = q.seed;
+    a.utt_ids = q.utt_ids;
+    a.tv = r.tv;
+    a.x = r.x;
+    a.x16 = r.x16;
+    a.ld16 = r.ld16;
+    a.bf16 = r.c->bf16;
+    if (int st = q_sample(a, r.B, r.T, r.nm, s)) return st;
+  } else if (int st = init_noise(r.x, r.x16, r.ld16, r.B, r.T, r.nm, q.seed, q.utt_ids, 1.0f / 1.2f, s, r.c->bf16)) {
+    return st;
+  }
+  SVC_HIP_CHECK(hipMemsetAsync(r.xp16, 0, (size_t)r.rows * r.ld16 * sizeof(f16), s));
+  return SVC_OK;
+}
+
+// steps K - 1 .. 0; the update draws its z on the device, keyed by seed, utterance id and step, unless `noise` holds it
+static int run_ddpm(SamplerRun& r, int K, const float* noise, uint64_t seed, const int32_t* utt_ids) {
+  svc_ctx* c = r.c;
+  for (int i = K - 1; i >= 0; --i) {
+    DdpmArgs a{};
+    a.sra = c->sra[i];
+    a.srm1 = c->srm1[i];
+    a.c1 = c->pc1[i];
+    a.c2 = c->pc2[i];
+    a.sigma = i > 0 ? expf(0.5f * c->plogvar[i]) : 0.0f;
+    a.seed = seed;
+    a.step = i;
+    a.bf16 = c->bf16;
+    for (int h = 0; h < r.sb.n; ++h) {
+      if (int st = r.denoise(h, r.x16, i, r.eps)) return st;
+      a.z = noise ? r.rowsf(noise + (size_t)(K - 1 - i) * r.rows * r.nm, h) : nullptr;
+      a.utt_ids = utt_ids ? utt_ids + r.sb.b0(h) : nullptr;
+      if (int st = ddpm_update(r.rowsf(r.x, h), r.rowsf(r.eps, h), r.rows16(r.x16, h), r.ld16,
+                               r.sb.b0(h + 1) - r.sb.b0(h), r.T, r.nm, a, r.sb.stream(h)))
+        return st;
+    }
+  }
+  return SVC_OK;
+}
+
+// The five PLMS combinations e' = (sum_j c[j] e_j) / div (modules/diffsvcrepo_inference.py:117-147): the first step's
+// predictor and corrector, then Adams-Bashforth of order 2, 3, 4 over the current eps and 1, 2, 3 earlier ones
+struct PlmsCoeffs {
+  int ne;
+  float div, c[4];
+};
+static constexpr PlmsCoeffs kPlmsCoeffs[5] = {
+    {1, 1.0f, {1.0f}}, {2, 2.0f, {1.0f, 1.0f}}, {2, 2.0f, {3.0f, -1.0f}}, {3, 12.0f, {23.0f, -16.0f, 5.0f}},
+    {4, 24.0f, {55.0f, -59.0f, 37.0f, -9.0f}}};
+
+// steps i = ((K - 1) / interval) * interval, ..., 0 from an empty history
+static int run_plms(SamplerRun& r, int K, int interval) {
+  const std::vector<float>& ac = r.c->alphas_cumprod_f32;
+  // the ring of epsilons, shared by the sub-batches: slot 0 takes this step's, slot k holds the one k <= nh steps back
+  int nh = 0, head = 0, st;
+  auto slot = [&](int back) { return r.hist[((head - back) % 5 + 5) % 5]; };
+  // sub-batch h's update of x, or with pred into xp / xp16, by a row of the table over the slots 0, dir, 2 dir, ...
+  auto update = [&](PlmsArgs p, const PlmsCoeffs& k, int h, int dir, bool pred) {
+    p.xin = r.rowsf(r.x, h);
+    p.xout = r.rowsf(pred ? r.xp : r.x, h);
+    p.x16 = r.rows16(pred ? r.xp16 : r.x16, h);
+    p.ne = k.ne;
+    p.div = k.div;
+    for (int j = 0; j < k.ne; ++j) {
+      p.e[j] = r.rowsf(slot(j * dir), h);
+      p.c[j] = k.c[j];
+    }
+    return p;
+  };
+  for (int i = ((K - 1) / interval) * interval; i >= 0; i -= interval) {
+    const int tp = i - interval > 0 ? i - interval : 0;
+    // get_x_pred coefficients in f32 exactly as the reference's tensor ops (:96-113)
+    const float a_t = ac[i], a_prev = ac[tp];
+    const float a_t_sq = sqrtf(a_t), a_prev_sq = sqrtf(a_prev);
+    PlmsArgs step{};
+    step.A = 1.0f / (a_t_sq * (a_t_sq + a_prev_sq));
+    step.Bc = 1.0f / (a_t_sq * (sqrtf((1.0f - a_prev) * a_t) + sqrtf((1.0f - a_t) * a_prev)));
+    step.d = a_prev - a_t;
+    step.ld16 = r.ld16;
+    step.bf16 = r.c->bf16;
+    for (int h = 0; h < r.sb.n; ++h) {
+      if (nh == 0) {
+        // No history: a predictor from eps(x, i) into xp / xp16, then x's update with the average of that eps and
+        // eps(xp, tp), which borrows the next slot (-1). Both calls are enqueued before the next sub-batch's.
+        const PlmsArgs q = update(step, kPlmsCoeffs[0], h, -1, true), p = update(step, kPlmsCoeffs[1], h, -1, false);
+        if ((st = r.denoise(h, r.x16, i, slot(0), &q))) return st;
+        st = r.denoise(h, r.xp16, tp, slot(-1), &p);
+      } else {
+        const PlmsArgs p = update(step, kPlmsCoeffs[1 + (nh < 3 ? nh : 3)], h, 1, false);
+        st = r.denoise(h, r.x16, i, slot(0), &p);
+      }
+      if (st) return st;
+    }
+    head = (head + 1) % 5;
+    nh = nh < 4 ? nh + 1 : 4;
+  }
+  return SVC_OK;
+}
 
 // The DPM-Solver++(2M) coefficients of the step t -> s < t (DpmArgs a, b; w0, w1 with the previous step's h_prev), in
 // f64 from the f32 alphas_cumprod table widened exactly, each rounded once: lambda = ln(ac / (1 - ac)) / 2,
@@ -232,220 +406,65 @@ static double dpm_step_coeffs(const std::vector<float>& ac, int t, int s, double
   return h;
 }
 
-static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* tv, int mode, int interval, int K,
-                       const float* x_T, const float* mel_src, const float* noise, uint64_t seed,
-                       const int32_t* utt_ids, float* x0, hipStream_t stream, const SolverSteps* sol = nullptr) {
+// Step j denoises at ts[j] and moves x to level ts[j + 1]: first order at j = 0 (no history yet), 2M from j = 1 when
+// order is 2; the last call returns its data prediction (sigma_next = 0), where the 2M extrapolation has no finite h.
+// One history buffer: D overwrites D_prev in place.
+static int run_solver(SamplerRun& r, const int32_t* ts, int n, int order) {
+  double h_prev = 0.0;
+  for (int j = 0; j < n; ++j) {
+    const int t = ts[j];
+    const bool last = j + 1 == n;
+    DpmArgs p{};
+    p.sra = r.c->sra[t];
+    p.srm1 = r.c->srm1[t];
+    p.final_step = last;
+    p.ld16 = r.ld16;
+    p.bf16 = r.c->bf16;
+    const bool second = !last && order == 2 && j > 0;
+    if (!last) h_prev = dpm_step_coeffs(r.c->alphas_cumprod_f32, t, ts[j + 1], second ? h_prev : 0.0, p);
+    for (int h = 0; h < r.sb.n; ++h) {
+      p.x = r.rowsf(r.x, h);
+      p.eps = r.rowsf(r.eps, h);
+      p.d_prev = second ? r.rowsf(r.hist[0], h) : nullptr;
+      p.d_out = order == 2 && j + 2 < n ? r.rowsf(r.hist[0], h) : nullptr;  // step j + 1 is a 2M step
+      p.x16 = last ? nullptr : r.rows16(r.x16, h);
+      if (int st = r.denoise(h, r.x16, t, r.eps, &p)) return st;
+    }
+  }
+  return SVC_OK;
+}
+
+static int sample_impl(svc_ctx* c, const float* cond, int B, int T, const int* tv, const SampleRequest& q, float* x0,
+                       hipStream_t s) {
+  const bool sol = q.kind == SAMPLER_SOLVER;
   SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
-  SVC_REQUIRE(K >= 1 && K <= c->steps, "sample: k_step %d outside [1, %d]", K, c->steps);
-  SVC_REQUIRE(sol || mode == SVC_MODE_DDPM || (mode == SVC_MODE_PLMS && interval >= 1), "sample: mode %d interval %d",
-              mode, interval);
-  SVC_REQUIRE(x_T || utt_ids, "sample: need x_T or utt_ids for device noise");
+  SVC_REQUIRE(q.K >= 1 && q.K <= c->steps, "sample: k_step %d outside [1, %d]", q.K, c->steps);
+  SVC_REQUIRE(sol || q.mode == SVC_MODE_DDPM || (q.mode == SVC_MODE_PLMS && q.interval >= 1),
+              "sample: mode %d interval %d", q.mode, q.interval);
+  SVC_REQUIRE(q.x_T || q.utt_ids, "sample: need x_T or utt_ids for device noise");
   // DDPM draws step noise on the device unless `noise` is given; that noise is keyed by utterance id
-  SVC_REQUIRE(sol || mode != SVC_MODE_DDPM || noise || utt_ids, "sample: DDPM without `noise` needs utt_ids");
+  SVC_REQUIRE(sol || q.mode != SVC_MODE_DDPM || q.noise || q.utt_ids, "sample: DDPM without `noise` needs utt_ids");
+  SamplerRun r{c, B, T, tv, B * T, c->n_mel, (int)round_up(c->n_mel, 8), x0};
+  int st = r.plan();
+  if (st || (st = project_cond(c, cond, B, T, r.bb, s)) || (st = set_start(r, q, s))) return st;
+  // Utterance-aligned sub-batches on their own streams, issued kernel by kernel in alternation: their launches overlap
+  // on the GPU, so one sub-batch's epilogue / prologue phases (HBM-bound, ~40 % of a denoiser GEMM launch at this size)
+  // run beside the other's MFMA phases (profiles/r02zf_streams_ab.txt: 2 streams +0.9 % over 3, 4: -15 %). Utterances
+  // are independent, so results are identical to a single stream; sampler_streams = 1 disables the split. Every loop
+  // visits the sub-batches in order within a step: the enqueue order decides what runs beside what.
+  if ((st = r.sb.fork(c, tuning().sampler_streams, B, s))) return st;
+  switch (q.kind) {
+    case SAMPLER_DDPM: st = run_ddpm(r, q.K, q.noise, q.seed, q.utt_ids); break;
+    case SAMPLER_PLMS: st = run_plms(r, q.K, q.interval); break;
+    case SAMPLER_SOLVER: st = run_solver(r, q.ts, q.n_ts, q.order); break;
+  }
+  return st ? st : r.sb.join();
+}
+
+static int sample_entry(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames, const SampleRequest& q,
+                        float* x0, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int rows = B * T, nm = c->n_mel, ld16 = (int)round_up(nm, 8);
-  DenoiseBufs bb;
-  f16 *x16, *xp16;
-  float *eps, *hist[5], *xp;
-  int st = c->ws.plan([&](Arena& ws) {
-    layout_denoise(c, ws, B, T, bb);
-    x16 = ws.get<f16>((size_t)rows * ld16);
-    eps = ws.get<float>((size_t)rows * nm);
-    for (int k = 0; k < 5; ++k) hist[k] = ws.get<float>((size_t)rows * nm);
-    xp = ws.get<float>((size_t)rows * nm);
-    xp16 = ws.get<f16>((size_t)rows * ld16);
-  });
-  if (st || (st = project_cond(c, cond, B, T, bb, s))) return st;
-  float* x = x0;  // the sampler state lives in the output buffer
-  SVC_HIP_CHECK(hipMemsetAsync(x16, 0, (size_t)rows * ld16 * sizeof(f16), s));  // zero pad channels
-  if (x_T) {
-    SVC_HIP_CHECK(hipMemcpyAsync(x, x_T, (size_t)rows * nm * 4, hipMemcpyDeviceToDevice, s));
-    if ((st = f32_to_f16(x, nm, x16, ld16, rows, nm, ld16, s, c->bf16))) return st;
-  } else if (mel_src) {
-    const float ac = c->alphas_cumprod_f32[K - 1];
-    QSampleArgs q{};
-    q.mel = mel_src;
-    q.mn = c->mel_min;
-    q.mx = c->mel_max;
-    q.noised = 1;
-    q.a = sqrtf(ac);
-    q.b = sqrtf(1.0f - ac);
-    q.seed = seed;
-    q.utt_ids = utt_ids;
-    q.tv = tv;
-    q.x = x;
-    q.x16 = x16;
-    q.ld16 = ld16;
-    q.bf16 = c->bf16;
-    if ((st = q_sample(q, B, T, nm, s))) return st;
-  } else {
-    if ((st = init_noise(x, x16, ld16, B, T, nm, seed, utt_ids, 1.0f / 1.2f, s, c->bf16))) return st;
-  }
-  SVC_HIP_CHECK(hipMemsetAsync(xp16, 0, (size_t)rows * ld16 * sizeof(f16), s));
-
-  // Utterance-aligned sub-batches on their own streams, issued kernel by kernel in alternation: their
-  // launches overlap on the GPU, so one sub-batch's epilogue / prologue phases (HBM-bound, ~40 % of a
-  // denoiser GEMM launch at this size) run beside the other's MFMA phases. Utterances are independent,
-  // so results are identical to a single stream. Default 2 (round-2 final code, alternating A/B on two boxes:
-  // +0.9 % over 3, 4: -15 %; profiles/r02zf_streams_ab.txt); sampler_streams = 1 disables the split.
-  SubBatches sb;
-  if ((st = sb.fork(c, tuning().sampler_streams, B, s))) return st;
-  const int S = sb.n;
-  struct Sub {
-    int B, b0;
-    size_t r0;
-  } sub[kMaxSubStreams];
-  for (int h = 0; h < S; ++h) {
-    sub[h].b0 = sb.b0(h);
-    sub[h].B = sb.b0(h + 1) - sub[h].b0;
-    sub[h].r0 = (size_t)sub[h].b0 * T;
-  }
-  auto sub_bufs = [&](const Sub& u) {
-    const size_t r = u.r0;
-    const int C = c->C;
-    return DenoiseBufs{bb.cp16 + r * 2 * C, bb.y16 + r * C, bb.g16 + r * C, bb.s16 + r * 3 * C, bb.u16 + r * 3 * C,
-                       bb.lo16 + r * C, bb.cp_ls, bb.g_ls};
-  };
-
-  if (sol) {
-    // Step j denoises at ts[j] and moves x to level ts[j + 1]: first order at j = 0 (no history yet), 2M from j = 1 when
-    // order is 2; the last call returns its data prediction (sigma_next = 0), where the 2M extrapolation has no finite h.
-    // One history buffer: D overwrites D_prev in place.
-    double h_prev = 0.0;
-    for (int j = 0; j < sol->n; ++j) {
-      const int t = sol->ts[j];
-      const bool last = j + 1 == sol->n;
-      DpmArgs p{};
-      p.sra = c->sra[t];
-      p.srm1 = c->srm1[t];
-      p.final_step = last;
-      p.ld16 = ld16;
-      p.bf16 = c->bf16;
-      const bool second = !last && sol->order == 2 && j > 0;
-      if (!last) h_prev = dpm_step_coeffs(c->alphas_cumprod_f32, t, sol->ts[j + 1], second ? h_prev : 0.0, p);
-      for (int h = 0; h < S; ++h) {
-        const Sub& u = sub[h];
-        const size_t r = u.r0;
-        DpmArgs q = p;
-        q.x = x + r * nm;
-        q.eps = eps + r * nm;
-        q.d_prev = second ? hist[0] + r * nm : nullptr;
-        q.d_out = sol->order == 2 && j + 2 < sol->n ? hist[0] + r * nm : nullptr;  // step j + 1 is a 2M step
-        q.x16 = last ? nullptr : x16 + r * ld16;
-        if ((st = denoise(c, sub_bufs(u), x16 + r * ld16, u.B, T, t, eps + r * nm, sb.stream(h),
-                          tv ? tv + u.b0 : nullptr, &q)))
-          return st;
-      }
-    }
-    return sb.join();
-  }
-  if (mode == SVC_MODE_DDPM) {
-    for (int i = K - 1; i >= 0; --i) {
-      for (int h = 0; h < S; ++h) {
-        const Sub& u = sub[h];
-        const size_t r = u.r0;
-        const hipStream_t us = sb.stream(h);
-        if ((st = denoise(c, sub_bufs(u), x16 + r * ld16, u.B, T, i, eps + r * nm, us, tv ? tv + u.b0 : nullptr)))
-          return st;
-        DdpmArgs a{};
-        a.sra = c->sra[i];
-        a.srm1 = c->srm1[i];
-        a.c1 = c->pc1[i];
-        a.c2 = c->pc2[i];
-        a.sigma = i > 0 ? expf(0.5f * c->plogvar[i]) : 0.0f;
-        a.z = noise ? noise + (size_t)(K - 1 - i) * rows * nm + r * nm : nullptr;
-        a.seed = seed;
-        a.utt_ids = utt_ids ? utt_ids + u.b0 : nullptr;
-        a.step = i;
-        a.bf16 = c->bf16;
-        if ((st = ddpm_update(x + r * nm, eps + r * nm, x16 + r * ld16, ld16, u.B, T, nm, a, us))) return st;
-      }
-    }
-    return sb.join();
-  }
-  // PLMS: history ring of 4 epsilons + the first step's predictor buffers (the ring position is shared)
-  int nh = 0, head = 0;  // hist slots: newest at hist[(head - 1) mod 5]
-  const std::vector<float>& ac = c->alphas_cumprod_f32;
-  for (int i = ((K - 1) / interval) * interval; i >= 0; i -= interval) {
-    const int tp = i - interval > 0 ? i - interval : 0;
-    // get_x_pred coefficients in f32 exactly as the reference's tensor ops (:96-113)
-    const float a_t = ac[i], a_prev = ac[tp];
-    const float a_t_sq = sqrtf(a_t), a_prev_sq = sqrtf(a_prev);
-    const float A = 1.0f / (a_t_sq * (a_t_sq + a_prev_sq));
-    const float Bc = 1.0f / (a_t_sq * (sqrtf((1.0f - a_prev) * a_t) + sqrtf((1.0f - a_t) * a_prev)));
-    const float d = a_prev - a_t;
-    for (int h = 0; h < S; ++h) {
-      const Sub& u = sub[h];
-      const size_t r = u.r0;
-      const hipStream_t us = sb.stream(h);
-      const DenoiseBufs ub = sub_bufs(u);
-      float* ecur = hist[head] + r * nm;
-      PlmsArgs p{};
-      p.bf16 = c->bf16;
-      p.d = d;
-      p.A = A;
-      p.Bc = Bc;
-      p.xin = x + r * nm;
-      p.xout = x + r * nm;
-      p.x16 = x16 + r * ld16;
-      p.ld16 = ld16;
-      auto H = [&](int back) { return hist[((head - back) % 5 + 5) % 5] + r * nm; };
-      // each update runs in (or right after) the denoise whose eps it consumes (denoise's plms argument)
-      if (nh == 0) {
-        PlmsArgs q = p;
-        q.e[0] = ecur;
-        q.c[0] = 1.0f;
-        q.ne = 1;
-        q.div = 1.0f;
-        q.xout = xp + r * nm;
-        q.x16 = xp16 + r * ld16;
-        if ((st = denoise(c, ub, x16 + r * ld16, u.B, T, i, ecur, us, tv ? tv + u.b0 : nullptr, &q)))
-          return st;
-        float* eprev = hist[(head + 1) % 5] + r * nm;
-        p.e[0] = ecur;
-        p.e[1] = eprev;
-        p.c[0] = 1.0f;
-        p.c[1] = 1.0f;
-        p.ne = 2;
-        p.div = 2.0f;
-        if ((st = denoise(c, ub, xp16 + r * ld16, u.B, T, tp, eprev, us, tv ? tv + u.b0 : nullptr, &p)))
-          return st;
-        continue;
-      } else if (nh == 1) {
-        p.e[0] = ecur;
-        p.e[1] = H(1);
-        p.c[0] = 3.0f;
-        p.c[1] = -1.0f;
-        p.ne = 2;
-        p.div = 2.0f;
-      } else if (nh == 2) {
-        p.e[0] = ecur;
-        p.e[1] = H(1);
-        p.e[2] = H(2);
-        p.c[0] = 23.0f;
-        p.c[1] = -16.0f;
-        p.c[2] = 5.0f;
-        p.ne = 3;
-        p.div = 12.0f;
-      } else {
-        p.e[0] = ecur;
-        p.e[1] = H(1);
-        p.e[2] = H(2);
-        p.e[3] = H(3);
-        p.c[0] = 55.0f;
-        p.c[1] = -59.0f;
-        p.c[2] = 37.0f;
-        p.c[3] = -9.0f;
-        p.ne = 4;
-        p.div = 24.0f;
-      }
-      if ((st = denoise(c, ub, x16 + r * ld16, u.B, T, i, ecur, us, tv ? tv + u.b0 : nullptr, &p)))
-        return st;
-    }
-    head = (head + 1) % 5;
-    nh = nh < 4 ? nh + 1 : 4;
-  }
-  return sb.join();
+  return with_frames(c, frames, B, T, x0, s, [&](const int* tv) { return sample_impl(c, cond, B, T, tv, q, x0, s); });
 }
 
 extern "C" {
@@ -456,35 +475,26 @@ svc_status svc_diffsvc_eps(svc_ctx* c, const float* cond, const float* x, int B,
   SVC_REQUIRE(c->has_mapper, "mapper weights not loaded");
   SVC_REQUIRE(t >= 0 && t < c->steps, "eps: t=%d", t);
   hipStream_t s = (hipStream_t)stream;
-  const int* tv;
-  RingRetire retire_(c->lens_main, s);
-  if (int st0 = stage_frames(c->lens_main, frames, B, T, s, &tv)) return st0;
-  const int rows = B * T, ld16 = (int)round_up(c->n_mel, 8);
-  DenoiseBufs bb;
-  f16* x16;
-  int st = c->ws.plan([&](Arena& ws) {
-    layout_denoise(c, ws, B, T, bb);
-    x16 = ws.get<f16>((size_t)rows * ld16);
+  return with_frames(c, frames, B, T, eps, s, [&](const int* tv) {
+    const int rows = B * T, ld16 = (int)round_up(c->n_mel, 8);
+    DenoiseBufs bb;
+    f16* x16;
+    int st = c->ws.plan([&](Arena& ws) {
+      layout_denoise(c, ws, B, T, bb);
+      x16 = ws.get<f16>((size_t)rows * ld16);
+    });
+    if (st || (st = project_cond(c, cond, B, T, bb, s))) return st;
+    if ((st = f32_to_f16(x, c->n_mel, x16, ld16, rows, c->n_mel, ld16, s, c->bf16))) return st;
+    return denoise(c, bb, x16, B, T, t, eps, s, tv);
   });
-  if (st || (st = project_cond(c, cond, B, T, bb, s))) return st;
-  if ((st = f32_to_f16(x, c->n_mel, x16, ld16, rows, c->n_mel, ld16, s, c->bf16))) return st;
-  if ((st = denoise(c, bb, x16, B, T, t, eps, s, tv))) return st;
-  return tv ? zero_tail_rows(eps, B, T, c->n_mel, tv, s) : SVC_OK;
 }
 
 svc_status svc_diffsvc_sample(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames, int mode,
                               int interval, const float* x_T, const float* noise, uint64_t seed,
                               const int32_t* utt_ids, float* x0, void* stream) {
   CTX_READY(c);
-  hipStream_t s = (hipStream_t)stream;
-  const int* tv;
-  RingRetire retire_(c->lens_main, s);
-  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
-  if (st ||
-      (st = sample_impl(c, cond, B, T, tv, mode, interval, c->steps, x_T, nullptr, noise, seed, utt_ids, x0, s)))
-    return st;
-  // frames past an utterance's end hold no sample: zero them
-  return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+  const SampleRequest q{c->steps, x_T, nullptr, seed, utt_ids, SampleRequest::of_mode(mode), mode, interval, noise};
+  return sample_entry(c, cond, B, T, frames, q, x0, stream);
 }
 
 svc_status svc_diffsvc_sample_from(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames, int mode,
@@ -494,14 +504,8 @@ svc_status svc_diffsvc_sample_from(svc_ctx* c, const float* cond, int B, int T, 
   CTX_READY(c);
   SVC_REQUIRE((mel_src != nullptr) != (x_start != nullptr), "sample_from: give exactly one of mel_src and x_start");
   SVC_REQUIRE(!mel_src || utt_ids, "sample_from: mel_src draws the forward noise on the device and needs utt_ids");
-  hipStream_t s = (hipStream_t)stream;
-  const int* tv;
-  RingRetire retire_(c->lens_main, s);
-  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
-  if (st ||
-      (st = sample_impl(c, cond, B, T, tv, mode, interval, k_step, x_start, mel_src, noise, seed, utt_ids, x0, s)))
-    return st;
-  return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+  const SampleRequest q{k_step, x_start, mel_src, seed, utt_ids, SampleRequest::of_mode(mode), mode, interval, noise};
+  return sample_entry(c, cond, B, T, frames, q, x0, stream);
 }
 
 svc_status svc_diffsvc_sample_steps(svc_ctx* c, const float* cond, int B, int T, const int32_t* frames,
@@ -519,15 +523,9 @@ svc_status svc_diffsvc_sample_steps(svc_ctx* c, const float* cond, int B, int T,
   }
   SVC_REQUIRE(!(mel_src && x_start), "sample_steps: give at most one of mel_src and x_start");
   SVC_REQUIRE(x_start || utt_ids, "sample_steps: the device draw (x_start NULL) needs utt_ids");
-  hipStream_t s = (hipStream_t)stream;
-  const int* tv;
-  RingRetire retire_(c->lens_main, s);
-  const SolverSteps sol{timesteps, n_steps, order};
-  int st = stage_frames(c->lens_main, frames, B, T, s, &tv);
-  if (st || (st = sample_impl(c, cond, B, T, tv, SVC_MODE_PLMS, 1, timesteps[0] + 1, x_start, mel_src, nullptr, seed,
-                              utt_ids, x0, s, &sol)))
-    return st;
-  return tv ? zero_tail_rows(x0, B, T, c->n_mel, tv, s) : SVC_OK;
+  const SampleRequest q{timesteps[0] + 1, x_start, mel_src, seed, utt_ids, SAMPLER_SOLVER,
+                        /* no mode, interval, noise */ 0, 0, nullptr, timesteps, n_steps, order};
+  return sample_entry(c, cond, B, T, frames, q, x0, stream);
 }
 
 // normalize_mel_channel (utils/acoustic_feature_extraction.py:75-80) with the context's statistics
@@ -550,3 +548,4 @@ svc_status svc_mel_normalize(svc_ctx* c, const float* mel, int B, int T, const i
 }
 
 }  // extern "C"
+

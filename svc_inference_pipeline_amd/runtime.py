@@ -24,6 +24,19 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _opt_ptr(t):
+    """_ptr of an optional device tensor, made contiguous."""
+    return _ptr(t.contiguous()) if t is not None else None
+
+
+def _draw_keys(utt_ids, draws, B, device):
+    """utt_ids as contiguous int32 (None stays None). What the device draws is keyed by utterance id: where it will
+    draw (`draws`), missing ids default to the batch positions."""
+    if utt_ids is None and draws:
+        utt_ids = torch.arange(B, device=device, dtype=torch.int32)
+    return utt_ids.to(torch.int32).contiguous() if utt_ids is not None else None
+
+
 def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -486,46 +499,30 @@ class SVCEngine:
             raise ValueError("diffsvc_sample: mel_src / x_start need k_step")
         if k_step is not None and (x_T is not None or (mel_src is None) == (x_start is None)):
             raise ValueError("diffsvc_sample: k_step takes exactly one of mel_src and x_start (and no x_T)")
-        if solver is not None:
-            if noise is not None:
-                raise ValueError("diffsvc_sample: `noise` with a solver (the solvers draw nothing per step)")
-            ts = solver_timesteps(self.cfg, k_step, solver_steps, solver_spacing)
-            return self._diffsvc_sample_steps(cond, ts, SOLVERS[solver], x_T if k_step is None else x_start, mel_src,
-                                              seed, utt_ids, frames)
+        if solver is not None and noise is not None:
+            raise ValueError("diffsvc_sample: `noise` with a solver (the solvers draw nothing per step)")
         x0 = torch.empty(B, T, self.cfg.mapper.n_mel, device=cond.device, dtype=torch.float32)
-        if utt_ids is None and ((x_T is None and x_start is None) or (noise is None and not fast_inference)):
-            # device noise (x_T, and DDPM's per-step z) is keyed by utterance id: default to batch positions
-            utt_ids = torch.arange(B, device=cond.device, dtype=torch.int32)
-        uid = utt_ids.to(torch.int32).contiguous() if utt_ids is not None else None
+        if solver is not None:
+            ts = solver_timesteps(self.cfg, k_step, solver_steps, solver_spacing)
+            # the state at level ts[0]; without one, mel_src noised to it or the device draw
+            start = x_T if k_step is None else x_start
+            uid = _draw_keys(utt_ids, start is None, B, cond.device)
+            _lib.call("svc_diffsvc_sample_steps", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32),
+                      (ctypes.c_int32 * len(ts))(*ts), len(ts), SOLVERS[solver], _opt_ptr(mel_src), _opt_ptr(start),
+                      ctypes.c_uint64(seed), _ptr(uid), _ptr(x0), _stream())
+            return x0
+        # the device draws x_T, and DDPM's per-step z
+        uid = _draw_keys(utt_ids, (x_T is None and x_start is None) or (noise is None and not fast_inference), B,
+                         cond.device)
         mode = MODE_PLMS if fast_inference else MODE_DDPM
         if k_step is not None:
             _lib.call("svc_diffsvc_sample_from", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32),
-                      mode, int(speedup), k_step,
-                      _ptr(mel_src.contiguous()) if mel_src is not None else None,
-                      _ptr(x_start.contiguous()) if x_start is not None else None,
-                      _ptr(noise.contiguous()) if noise is not None else None, ctypes.c_uint64(seed), _ptr(uid),
-                      _ptr(x0), _stream())
-            return x0
-        _lib.call("svc_diffsvc_sample", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32), mode,
-                  int(speedup),
-                  _ptr(x_T.contiguous()) if x_T is not None else None,
-                  _ptr(noise.contiguous()) if noise is not None else None, ctypes.c_uint64(seed), _ptr(uid),
-                  _ptr(x0), _stream())
-        return x0
-
-    def _diffsvc_sample_steps(self, cond, ts, order, start, mel_src, seed, utt_ids, frames):
-        """svc_diffsvc_sample_steps over the timesteps ts from the state `start` at level ts[0], or from mel_src noised
-        to it, or from the device draw."""
-        B, T, _ = cond.shape
-        if utt_ids is None and start is None:  # the start state is drawn on the device: keyed by batch position
-            utt_ids = torch.arange(B, device=cond.device, dtype=torch.int32)
-        uid = utt_ids.to(torch.int32).contiguous() if utt_ids is not None else None
-        x0 = torch.empty(B, T, self.cfg.mapper.n_mel, device=cond.device, dtype=torch.float32)
-        _lib.call("svc_diffsvc_sample_steps", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32),
-                  (ctypes.c_int32 * len(ts))(*ts), len(ts), order,
-                  _ptr(mel_src.contiguous()) if mel_src is not None else None,
-                  _ptr(start.contiguous()) if start is not None else None, ctypes.c_uint64(seed), _ptr(uid), _ptr(x0),
-                  _stream())
+                      mode, int(speedup), k_step, _opt_ptr(mel_src), _opt_ptr(x_start), _opt_ptr(noise),
+                      ctypes.c_uint64(seed), _ptr(uid), _ptr(x0), _stream())
+        else:
+            _lib.call("svc_diffsvc_sample", self._ctx, _ptr(cond), B, T, _host_lengths(frames, B, ctypes.c_int32), mode,
+                      int(speedup), _opt_ptr(x_T), _opt_ptr(noise), ctypes.c_uint64(seed), _ptr(uid), _ptr(x0),
+                      _stream())
         return x0
 
     def bigvgan(self, x0, return_mel=False, frames=None):
