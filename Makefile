@@ -47,6 +47,13 @@ build/retrieve.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
 	@python3 tools/check_kernel_resources.py build/$*.res '(knn_topk|retrieve_blend|index_norms)_kernel' 256 || { rm -f $@; exit 1; }
 
+# index compaction: index_sum keeps a row's 32 int64 column sums per lane (64 registers) under two rows of loads in
+# flight; a spill would put the streaming loop on scratch
+build/index_kmeans.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include/svc_hip.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
+	@python3 tools/check_kernel_resources.py build/$*.res '(index_\w+|inertia_\w+)_kernel' 128 || { rm -f $@; exit 1; }
+
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC $(OBJS) -o $@
 

@@ -37,6 +37,9 @@
  *   svc_content_retrieve <- no counterpart in the reference: RVC's feature index (index_rate), between the content
  *                          stage and svc_condition (each content frame blended with its k nearest frames of the
  *                          target singer's own recordings; svc_index_norms prepares an index)
+ *   svc_index_kmeans    <- no counterpart in the reference: RVC's k-means compaction of a large feature index, at
+ *                          enrolment (the searched rows become centroids of all of a singer's frames;
+ *                          svc_index_assign and svc_index_update are its two steps)
  *
  * Conventions
  *   - Tensors are caller-owned DEVICE buffers, time-major: row = b*T + t, channels contiguous.
@@ -498,6 +501,67 @@ svc_status svc_content_retrieve(svc_ctx* ctx, const void* content16, int B, int 
                                 const int32_t* sel, int D, int ld, const void* index16, const float* norms, int64_t N,
                                 int ld_index, int k, double rate, double dist_floor, void* out16, int ld_out,
                                 int32_t* idx_out, float* dist_out, void* stream);
+
+/* Index compaction (RVC fits k-means centres to a large feature index): Lloyd's iteration over a singer's content
+   frames, so that the rows svc_content_retrieve searches are K centroids covering all N frames instead of a strided
+   sample of them. fp16 rows only. Shared by the three entry points below: rows16 is binary16 [N] rows of ld >= D
+   halves, N in [1, 2^22]; K in [1, min(N, 2^20)]; D a multiple of 8 in [8, 2048]; every set of rows (rows16, centroids)
+   starts its rows on 16-byte boundaries (ld % 8 == 0, an aligned pointer). Scratch comes from the context's workspace
+   arena through each call's own buffer list, so the calls are ordered with the other stages that use it. All work is
+   enqueued on the stream: no host synchronisation, no random numbers. The context need not be finalized.
+   SVC_ERR_INVALID before any HIP call: a null context or required pointer; N, K, D, iters outside the ranges above;
+   ld < D or rows that do not start on 16-byte boundaries; an output that overlaps an input it is not allowed to be;
+   a context with "operands.bf16" (fp16 only: the message says so).
+
+   Part 1, the assignment. cent16: binary16 [K] rows of ld_cent halves, cent_norms f32 [K] (svc_index_norms of them).
+     labels[r] (device int32 [N]) = the j smallest under the total order (s_j, j), s_j = cent_norms[j] - 2 * dot(x_r,
+            c_j): svc_content_retrieve's score exactly (f16 products accumulated in f32 on v_mfma_f32_16x16x32_f16 in
+            ascending K, the same for a row wherever it sits in a tile), compared as f32, an equal s going to the lower
+            j. The labels therefore do not depend on the tiling, on "tune.retrieve_splits" or on the chunks of rows in
+            which N is walked (2^18 rows per launch, fewer when the splits are forced high).
+     counts[j] (optional, device int32 [K]) = the number of rows labelled j (integer atomics).
+     inertia[0] (optional, device f64) = sum_r max((float)|x_r|^2 + s_label(r), 0): |x_r|^2 an f32 sum in
+            svc_content_retrieve's order for |q|^2, each term f32, the terms added in f64 in an order fixed by N alone
+            (4096 terms per workgroup, a fixed tree), so the value is bit-identical from run to run.
+   Launches: index_prep, then per chunk knn_topk (svc_content_retrieve's kernel as it stands: rows as queries, centroids
+   as the index) and index_label (rank 0 of the splits' candidates), then inertia_part / inertia_final where asked.
+   Non-finite rows are the caller's error (such a row is labelled 0; never an access outside the buffers). */
+svc_status svc_index_assign(svc_ctx* ctx, const void* rows16, int64_t N, int D, int ld, const void* cent16,
+                            const float* cent_norms, int K, int ld_cent, int32_t* labels, int32_t* counts,
+                            double* inertia, void* stream);
+
+/* Part 2, the centroid update: the mean of every cluster, computed exactly and therefore independent of the order in
+   which its rows are met. labels: device int32 [N]; prev16: the previous centroids, [K] rows of ld_prev halves.
+     I(v)      = v * 2^24, an integer for every finite binary16 value, |I| < 2^40;
+     S[j][c]   = sum of I(x_r[c]) over the rows with labels[r] == j: exact in int64 (N <= 2^22);
+     out[j][c] = (half)(float)(((double)S[j][c] / (double)count_j) * 2^-24): the int64 -> f64 conversion, the f64
+                 division and the f32 and f16 conversions each round to nearest even;
+     a centroid with count_j == 0 keeps prev16's row bit for bit;
+     norms_out[j] (f32 [K]) = svc_index_norms' arithmetic on the new row; counts[j] (optional, int32 [K]) = count_j.
+   out16 ([K] rows of ld_out halves; columns at or past D are never touched) may be prev16 itself (the same pointer and
+   ld_out == ld_prev); any other overlap with prev16, and any with rows16, is an error. A label outside [0, K) is the
+   caller's error: its row joins no cluster, and nothing outside the buffers is touched.
+   Launches: index_hist, index_scan and index_scatter group the row numbers by label (counts, an exclusive scan, an
+   integer cursor per cluster); index_sum gives every cluster one workgroup per 1024 member rows, which streams whole
+   rows in 16-byte pieces into int64 sums and writes the f16 row; index_combine (only when N > 1024) adds the int64
+   partial rows of the clusters that had more than one workgroup; index_rownorms writes the new rows' norms. */
+svc_status svc_index_update(svc_ctx* ctx, const void* rows16, int64_t N, int D, int ld, const int32_t* labels, int K,
+                            const void* prev16, int ld_prev, void* out16, int ld_out, float* norms_out, int32_t* counts,
+                            void* stream);
+
+/* Part 3, the loop. cent16 ([K] rows of ld_cent halves) and cent_norms (f32 [K]) receive the result.
+     centroid i starts as row floor(i * N / K) of rows16: the rule by which SVCPipeline.enroll(index_max_rows=K) thins
+     an index, so iters = 0 returns that index (rows and svc_index_norms) bit for bit;
+     iters times (0 <= iters <= 1000): svc_index_assign, then svc_index_update in place;
+     one last svc_index_assign against the final centroids fills labels (optional, int32 [N]), counts (optional, int32
+     [K]) and the last inertia. inertia (optional, device f64 [iters + 1]): entry i is the assignment's inertia against
+     the centroids after i updates.
+   There is no early stop: a converged state is a fixed point of assign + update, so further iterations change nothing.
+   The result equals composing the two calls above by hand, bit for bit. cent16 must not overlap rows16.
+   Measured on MI355X (tools/kmeans_bench.py, profiles/kmeans_bench.json). */
+svc_status svc_index_kmeans(svc_ctx* ctx, const void* rows16, int64_t N, int D, int ld, int K, int iters, void* cent16,
+                            int ld_cent, float* cent_norms, int32_t* labels, int32_t* counts, double* inertia,
+                            void* stream);
 
 /* ---------------- op-level entry points (used by the parity tests; weights are unpacked f32 device arrays) */
 /* y[B*T_out][Cout] = conv1d(x[B*T_in][Cin]) ; w [Cout][Cin][k] ; act 0 none / 1 gelu / 2 relu */

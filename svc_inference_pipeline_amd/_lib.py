@@ -69,6 +69,12 @@ PROTOTYPES = {
     "svc_content_retrieve": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                      c_void_p, c_int64, c_int, c_int, c_double, c_double, c_void_p, c_int, c_void_p,
                                      c_void_p, c_void_p]),
+    "svc_index_assign": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
+    "svc_index_update": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                 c_int, c_void_p, c_void_p, c_void_p]),
+    "svc_index_kmeans": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "svc_op_conv1d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                               c_int, c_void_p, c_void_p]),
     "svc_op_conv_transpose1d": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

@@ -105,9 +105,19 @@ int loudness_match(const float* wav, const float* src, int B, int64_t S, int64_t
 // retrieve.hip: feature retrieval. table (device): int32 frames[B], then int32 sel[B]
 int index_norms(const f16* x, int64_t N, int D, int ld, float* norms, hipStream_t s);
 int retrieve_splits(int M, int64_t N);
+int knn_topk(const f16* q, int M, int T, int D, int ld, const int* table, int B, const f16* x, const float* norms, int N,
+             int ld_index, int n_splits, float* cand_s, int* cand_j, hipStream_t s);
 int content_retrieve(const f16* q, int B, int T, int D, int ld, const int* table, const f16* x, const float* norms,
                      int N, int ld_index, int k, double rate, double dist_floor, f16* out, int ld_out, int* idx_out,
                      float* dist_out, Arena& ws, hipStream_t s);
+// index_kmeans.hip: a retrieval index compacted by Lloyd's iteration (svc_index_assign / _update / _kmeans). Every
+// function lays its scratch out on the arena it is given (one plan per call)
+int index_assign(const f16* x, int64_t N, int D, int ld, const f16* cent, const float* cnorms, int K, int ld_cent,
+                 int* labels, int* counts, double* inertia, Arena& ws, hipStream_t s);
+int index_update(const f16* x, int64_t N, int D, int ld, const int* labels, int K, const f16* prev, int ld_prev, f16* out,
+                 int ld_out, float* norms_out, int* counts, Arena& ws, hipStream_t s);
+int index_kmeans(const f16* x, int64_t N, int D, int ld, int K, int iters, f16* cent, int ld_cent, float* cnorms,
+                 int* labels, int* counts, double* inertia, Arena& ws, hipStream_t s);
 int load_pcm(StageRing* ring, const int* device, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
              const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src, int64_t S_src,
              float* y_src, int sr_mono, int64_t S_mono, float* y_mono, float* y_mono_float, bool ex, int32_t* info,

@@ -355,13 +355,25 @@ int retrieve_splits(int M, int64_t N) {
   return std::max(1, std::min(std::min(want, tiles), kMaxSplits));
 }
 
+// The distance GEMM with the selection epilogue, as one launch: cand_s / cand_j [M][n_splits][8] (content_retrieve's
+// queries; index_assign's rows against the centroids, index_kmeans.hip)
+int knn_topk(const f16* q, int M, int T, int D, int ld, const int* table, int B, const f16* x, const float* norms, int N,
+             int ld_index, int n_splits, float* cand_s, int* cand_j, hipStream_t s) {
+  const int qtiles = cdiv(M, kQT);
+  const int tok = prof_begin("knn_topk", 2.0 * M * (double)N * D, ((double)M + (double)N * qtiles) * D * 2.0, s);
+  hipLaunchKernelGGL(knn_topk_kernel, dim3((unsigned)(qtiles * n_splits)), dim3(kThreads), 0, s, q, M, T, D, ld, table,
+                     table + B, x, norms, N, ld_index, n_splits, cand_s, cand_j);
+  prof_end(tok, s);
+  SVC_LAUNCH_CHECK();
+  return SVC_OK;
+}
+
 // table (device): int32 frames[B], then int32 sel[B], staged by the caller. The candidates come from ws.
 int content_retrieve(const f16* q, int B, int T, int D, int ld, const int* table, const f16* x, const float* norms,
                      int N, int ld_index, int k, double rate, double dist_floor, f16* out, int ld_out, int* idx_out,
                      float* dist_out, Arena& ws, hipStream_t s) {
   const int M = B * T;
   const int n_splits = retrieve_splits(M, N);
-  const int qtiles = cdiv(M, kQT);
   float* cand_s = nullptr;
   int* cand_j = nullptr;
   if (int st = ws.plan([&](Arena& a) {
@@ -371,13 +383,7 @@ int content_retrieve(const f16* q, int B, int T, int D, int ld, const int* table
     return st;
   const int* frames = table;
   const int* sel = table + B;
-  {
-    const int tok = prof_begin("knn_topk", 2.0 * M * (double)N * D, ((double)M + (double)N * qtiles) * D * 2.0, s);
-    hipLaunchKernelGGL(knn_topk_kernel, dim3((unsigned)(qtiles * n_splits)), dim3(kThreads), 0, s, q, M, T, D, ld,
-                       frames, sel, x, norms, N, ld_index, n_splits, cand_s, cand_j);
-    prof_end(tok, s);
-    SVC_LAUNCH_CHECK();
-  }
+  if (int st = knn_topk(q, M, T, D, ld, table, B, x, norms, N, ld_index, n_splits, cand_s, cand_j, s)) return st;
   const int tok = prof_begin("retrieve_blend", 2.0 * M * (double)k * D, (double)M * (k + 2.0) * D * 2.0, s);
   hipLaunchKernelGGL(retrieve_blend_kernel, dim3((unsigned)cdiv(M, kThreads / 64)), dim3(kThreads), 0, s, q, M, T, D, ld,
                      frames, sel, x, N, ld_index, n_splits, cand_s, cand_j, k, (float)rate, (float)(1.0 - rate),

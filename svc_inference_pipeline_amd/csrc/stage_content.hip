@@ -525,6 +525,84 @@ svc_status svc_content_retrieve(svc_ctx* c, const void* content16, int B, int T,
                           norms, (int)N, ld_index, k, rate, dist_floor, (f16*)out16, ld_out, idx_out, dist_out, c->ws, s);
 }
 
+// ---------------------------------------------------------------------------- index compaction (k-means)
+// svc_index_norms' checks of one set of f16 rows, under the entry point's name
+#define INDEX_ROWS_OK(fn, what, ptr, ldv, D)                                                                      \
+  do {                                                                                                            \
+    SVC_REQUIRE((ldv) >= (D), fn ": " what " ld=%d < D=%d", (ldv), (D));                                          \
+    SVC_REQUIRE((ldv) % 8 == 0 && aligned16(ptr), fn ": " what " rows must start on 16-byte boundaries (ld=%d)", \
+                (ldv));                                                                                           \
+  } while (0)
+#define INDEX_SHAPE_OK(fn, N, D, K)                                                                              \
+  do {                                                                                                           \
+    SVC_REQUIRE((N) >= 1 && (N) <= (1LL << 22), fn ": N=%lld (1 <= N <= 2^22)", (long long)(N));                 \
+    SVC_REQUIRE((D) >= 8 && (D) <= 2048 && (D) % 8 == 0, fn ": D=%d (a multiple of 8 in [8, 2048])", (D));       \
+    SVC_REQUIRE((K) >= 1 && (K) <= (N) && (K) <= (1 << 20), fn ": K=%d (1 <= K <= min(N, 2^20), N=%lld)", (K),   \
+                (long long)(N));                                                                                 \
+  } while (0)
+
+static bool disjoint(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 + na <= b0 || b0 + nb <= a0;
+}
+static size_t rows_bytes(int64_t n, int ld, int D) { return ((size_t)(n - 1) * (size_t)ld + (size_t)D) * 2; }
+
+svc_status svc_index_assign(svc_ctx* c, const void* rows16, int64_t N, int D, int ld, const void* cent16,
+                            const float* cent_norms, int K, int ld_cent, int32_t* labels, int32_t* counts,
+                            double* inertia, void* stream) {
+  SVC_REQUIRE(c, "index_assign: null context");
+  SVC_REQUIRE(rows16 && cent16 && cent_norms && labels, "index_assign: null %s",
+              !rows16 ? "rows16" : !cent16 ? "cent16" : !cent_norms ? "cent_norms" : "labels");
+  INDEX_SHAPE_OK("index_assign", N, D, K);
+  INDEX_ROWS_OK("index_assign", "rows16", rows16, ld, D);
+  INDEX_ROWS_OK("index_assign", "cent16", cent16, ld_cent, D);
+  SVC_REQUIRE(!c->bf16 && cfgv(c, "operands.bf16", 0) == 0, "index_assign: fp16 only (this context has operands.bf16)");
+  TuningScope tuning_scope_(&c->tune);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  return index_assign((const f16*)rows16, N, D, ld, (const f16*)cent16, cent_norms, K, ld_cent, labels, counts, inertia,
+                      c->ws, (hipStream_t)stream);
+}
+
+svc_status svc_index_update(svc_ctx* c, const void* rows16, int64_t N, int D, int ld, const int32_t* labels, int K,
+                            const void* prev16, int ld_prev, void* out16, int ld_out, float* norms_out, int32_t* counts,
+                            void* stream) {
+  SVC_REQUIRE(c, "index_update: null context");
+  SVC_REQUIRE(rows16 && labels && prev16 && out16 && norms_out, "index_update: null %s",
+              !rows16 ? "rows16" : !labels ? "labels" : !prev16 ? "prev16" : !out16 ? "out16" : "norms_out");
+  INDEX_SHAPE_OK("index_update", N, D, K);
+  INDEX_ROWS_OK("index_update", "rows16", rows16, ld, D);
+  INDEX_ROWS_OK("index_update", "prev16", prev16, ld_prev, D);
+  INDEX_ROWS_OK("index_update", "out16", out16, ld_out, D);
+  SVC_REQUIRE((out16 == prev16 && ld_out == ld_prev) ||
+                  disjoint(out16, rows_bytes(K, ld_out, D), prev16, rows_bytes(K, ld_prev, D)),
+              "index_update: out16 overlaps prev16 without being prev16");
+  SVC_REQUIRE(disjoint(out16, rows_bytes(K, ld_out, D), rows16, rows_bytes(N, ld, D)),
+              "index_update: out16 overlaps rows16");
+  SVC_REQUIRE(!c->bf16 && cfgv(c, "operands.bf16", 0) == 0, "index_update: fp16 only (this context has operands.bf16)");
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  return index_update((const f16*)rows16, N, D, ld, labels, K, (const f16*)prev16, ld_prev, (f16*)out16, ld_out,
+                      norms_out, counts, c->ws, (hipStream_t)stream);
+}
+
+svc_status svc_index_kmeans(svc_ctx* c, const void* rows16, int64_t N, int D, int ld, int K, int iters, void* cent16,
+                            int ld_cent, float* cent_norms, int32_t* labels, int32_t* counts, double* inertia,
+                            void* stream) {
+  SVC_REQUIRE(c, "index_kmeans: null context");
+  SVC_REQUIRE(rows16 && cent16 && cent_norms, "index_kmeans: null %s",
+              !rows16 ? "rows16" : !cent16 ? "cent16" : "cent_norms");
+  INDEX_SHAPE_OK("index_kmeans", N, D, K);
+  SVC_REQUIRE(iters >= 0 && iters <= 1000, "index_kmeans: iters=%d (0 <= iters <= 1000)", iters);
+  INDEX_ROWS_OK("index_kmeans", "rows16", rows16, ld, D);
+  INDEX_ROWS_OK("index_kmeans", "cent16", cent16, ld_cent, D);
+  SVC_REQUIRE(disjoint(cent16, rows_bytes(K, ld_cent, D), rows16, rows_bytes(N, ld, D)),
+              "index_kmeans: cent16 overlaps rows16");
+  SVC_REQUIRE(!c->bf16 && cfgv(c, "operands.bf16", 0) == 0, "index_kmeans: fp16 only (this context has operands.bf16)");
+  TuningScope tuning_scope_(&c->tune);
+  SVC_HIP_CHECK(hipSetDevice(c->device));
+  return index_kmeans((const f16*)rows16, N, D, ld, K, iters, (f16*)cent16, ld_cent, cent_norms, labels, counts, inertia,
+                      c->ws, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------- conditioner
 svc_status svc_condition_indices(svc_ctx* c, const double* f0, const float* energy, int n, int32_t* melody_idx,
                                  int32_t* loudness_idx, void* stream) {

@@ -30,7 +30,7 @@ from . import config as C
 from . import weights as W
 from .pipeline import SVCPipeline, hubert_content_type, wants_float16k
 from .runtime import K_STEP_MELS, SVCEngine, check_k_step, check_k_step_mel, mel_frames
-from .singers import SingerF0Table, check_index_rate
+from .singers import INDEX_COMPACT, SingerF0Table, check_index_compact, check_index_rate
 
 
 def build_engine(cfg, device=0, mapper_ckpt=None, vocoder_ckpt=None, whisper_ckpt=None, random_weights=None, seed=0,
@@ -190,6 +190,15 @@ def build_parser():
     ap.add_argument("--index", action="store_true",
                     help="with --enroll: also build the singer's retrieval index from the content frames of the "
                          "recordings (needs --singer-index to keep it)")
+    ap.add_argument("--index-max-rows", type=int, default=None, metavar="N",
+                    help="with --enroll --index: an index of more than N content frames is compacted to N rows "
+                         "(default: every frame is kept)")
+    ap.add_argument("--index-compact", default=None, choices=INDEX_COMPACT,
+                    help="with --enroll --index: how a larger index is brought down to --index-max-rows: 'stride' "
+                         "keeps rows floor(i * frames / N) (the default), 'kmeans' replaces the frames by the N k-means "
+                         "centroids of all of them (on the GPU). Audible benefit is unverified")
+    ap.add_argument("--index-iters", type=int, default=None, metavar="N",
+                    help="with --index-compact kmeans: rounds of Lloyd's iteration, 0..1000 (default 10)")
     ap.add_argument("--singer-index", default=None, metavar="FILE",
                     help="per-singer retrieval indexes (.npz, singers.SingerIndexTable): loaded when the file exists, "
                          "and saved after --enroll --index")
@@ -215,14 +224,17 @@ def build_parser():
 
 
 def enroll_singer(engine, cfg, singer_name, wav_paths, f0_method="parselmouth", table_path=None, index=False,
-                  index_path=None):
+                  index_path=None, index_max_rows=None, index_compact=None, index_iters=None):
     """--enroll: SVCPipeline.enroll of the named singer from wav files -> the table entry; the table is saved to
-    table_path where given. index: also the singer's retrieval index (--index), saved to index_path where given."""
+    table_path where given. index: also the singer's retrieval index (--index), saved to index_path where given;
+    index_max_rows / index_compact / index_iters: SVCPipeline.enroll's, passed on where given."""
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
-    entry = SVCPipeline(engine, f0_method=f0_method).enroll(int(singers[singer_name]), sources=list(wav_paths),
-                                                            **(dict(index=True) if index else {}))
+    kw = dict(index=True) if index else {}
+    kw.update({k: v for k, v in (("index_max_rows", index_max_rows), ("index_compact", index_compact),
+                                 ("index_iters", index_iters)) if v is not None})
+    entry = SVCPipeline(engine, f0_method=f0_method).enroll(int(singers[singer_name]), sources=list(wav_paths), **kw)
     if table_path:
         engine.singer_f0.save(table_path)
     if index and index_path:
@@ -270,6 +282,16 @@ def main(argv=None):
         ap.error(f"--index-rate: {exc}")
     if args.index and not args.enroll:
         ap.error("--index needs --enroll")
+    for flag, val in (("--index-max-rows", args.index_max_rows), ("--index-compact", args.index_compact),
+                      ("--index-iters", args.index_iters)):
+        if val is not None and not (args.enroll and args.index):
+            ap.error(f"{flag} needs --enroll --index")
+    if args.index_max_rows is not None and args.index_max_rows < 1:
+        ap.error("--index-max-rows: at least 1")
+    try:
+        check_index_compact(args.index_compact or "stride", 10 if args.index_iters is None else args.index_iters)
+    except ValueError as exc:
+        ap.error(f"--index-iters: {exc}")
     try:
         if C.check_solver(args.solver, args.solver_steps) is not None:
             C.solver_timesteps(cfg, args.k_step, args.solver_steps)
@@ -285,7 +307,8 @@ def main(argv=None):
         engine.load_singer_index(args.singer_index)
     if args.enroll:
         ent = enroll_singer(engine, cfg, args.singer, args.enroll, args.f0_method, args.singer_f0, index=args.index,
-                            index_path=args.singer_index)
+                            index_path=args.singer_index, index_max_rows=args.index_max_rows,
+                            index_compact=args.index_compact, index_iters=args.index_iters)
         print(f"Enrolled {args.singer}: voiced F0 median {ent['median']:.3f} Hz over {ent['voiced']} voiced of "
               f"{ent['frames']} frames, {ent['n_utts']} file(s)", flush=True)
         if not args.wav:

@@ -31,7 +31,7 @@ import torch
 from .audio import check_loudness_mix
 from .config import check_solver, solver_timesteps
 from .runtime import SVCEngine, check_k_step, check_k_step_mel, mel_frames
-from .singers import check_index_rate
+from .singers import check_index_compact, check_index_rate
 
 WHISPER_WINDOW = 478720       # 16 kHz samples per long-input window (29.92 s)
 WINDOW_MEL_FRAMES = 2805      # = 1496 encoder frames * 15 / 8
@@ -165,7 +165,7 @@ class SVCPipeline:
         return content
 
     def enroll(self, singer, sources=None, wavs24=None, max_batch=16, index=False, index_max_rows=None,
-               wavs16=None, wavs16_float=None):
+               wavs16=None, wavs16_float=None, index_compact="stride", index_iters=10):
         """Measure a singer's voiced F0 median from that singer's own recordings and record it as the singer's pitch
         target (utils/acoustic_feature_extraction.py:21-30 on the GPU): wav files (`sources`: paths, bytes or
         memoryviews, decoded by audio.load_batch) or 24 kHz f32 device tensors (`wavs24`), in ragged chunks of at most
@@ -177,7 +177,12 @@ class SVCPipeline:
         (rows, their svc_index_norms, n_utts, frames, content types), which `index_rate=` on the conversion entry points
         searches. With `wavs24` the 16 kHz copies are needed too: `wavs16` (and `wavs16_float` for ContentVec), as
         convert_ragged takes them; `sources` are decoded to all of them. index_max_rows: an index of N > index_max_rows
-        rows keeps rows floor(i * N / index_max_rows), i < index_max_rows. The F0 entry is what it is without index."""
+        rows keeps rows floor(i * N / index_max_rows), i < index_max_rows (index_compact="stride", the default), or
+        is replaced by the k-means centroids of all N rows (index_compact="kmeans": engine.index_kmeans with K =
+        index_max_rows and index_iters rounds of Lloyd's iteration from those same strided rows; centroids that end
+        without a row are dropped, and the entry records {"method", "iters", "inertia_first", "inertia_last",
+        "dropped"} under "compact"). With N <= index_max_rows both modes keep every row. The F0 entry is what it is
+        without index."""
         e = self.engine
         if (sources is None) == (wavs24 is None):
             raise ValueError("enroll: give either sources (wav files) or wavs24 (24 kHz tensors)")
@@ -185,6 +190,7 @@ class SVCPipeline:
             raise ValueError("enroll: max_batch >= 1")
         if index_max_rows is not None and int(index_max_rows) < 1:
             raise ValueError("enroll: index_max_rows >= 1")
+        index_compact, index_iters = check_index_compact(index_compact, index_iters)
         if index and getattr(e, "operands", "fp16") == "bf16":
             raise ValueError("enroll: index=True takes fp16 content (this engine runs operands='bf16')")
         if index and sources is None and wavs16 is None:
@@ -223,11 +229,20 @@ class SVCPipeline:
             if index:
                 x = torch.cat(crows).contiguous()
                 N = x.shape[0]
-                if index_max_rows is not None and N > int(index_max_rows):
+                norms = compact = None
+                if index_max_rows is not None and N > int(index_max_rows) and index_compact == "kmeans":
+                    cent, cnorms, counts, inertia = e.index_kmeans(x, int(index_max_rows), index_iters)
+                    live = counts > 0
+                    x, norms = cent[live].contiguous(), cnorms[live].contiguous()
+                    inertia = inertia.tolist()
+                    compact = dict(method="kmeans", iters=index_iters, inertia_first=inertia[0],
+                                   inertia_last=inertia[-1], dropped=int(index_max_rows) - int(x.shape[0]))
+                elif index_max_rows is not None and N > int(index_max_rows):
                     keep = [i * N // int(index_max_rows) for i in range(int(index_max_rows))]
                     x = x[torch.tensor(keep, device=x.device)].contiguous()
-                e.singer_index.set(singer, x, e.index_norms(x), n_utts=len(wavs24), frames=N,
-                                   content_types=sorted(e.cfg.mapper.content_feature))
+                e.singer_index.set(singer, x, e.index_norms(x) if norms is None else norms, n_utts=len(wavs24),
+                                   frames=N, content_types=sorted(e.cfg.mapper.content_feature),
+                                   **({} if compact is None else dict(compact=compact)))
             return entry
 
     def content(self, wav16, T, wav16_float=None):

@@ -674,6 +674,72 @@ class SVCEngine:
                   out.stride(1), _ptr(idx), _ptr(d2), _stream())
         return (out, idx, d2) if return_neighbours else out
 
+    def _index_rows(self, name, what, x16, D=None):
+        """f16 [n, D] with contiguous rows (a column slice of a wider buffer is fine), fp16 engines only"""
+        if self.operands != "fp16":
+            raise ValueError(f"{name}: fp16 rows only (this engine runs operands='bf16')")
+        if x16.dim() != 2 or x16.dtype != torch.float16 or x16.stride(1) != 1 or (D is not None and x16.shape[1] != D):
+            raise ValueError(f"{name}: {what} must be f16 [n, {'D' if D is None else D}] with contiguous rows")
+        return x16.shape
+
+    def index_assign(self, rows, centroids, norms, return_counts=False, return_inertia=False):
+        """Lloyd's assignment (svc_index_assign): rows f16 [N, D] against centroids f16 [K, D] with norms =
+        index_norms(centroids) -> labels int32 [N], each row's nearest centroid under content_retrieve's own score and
+        order (an equal score goes to the lower j). Also, where asked, counts int32 [K] and inertia f64 [1] (the sum
+        of the rows' clamped squared distances, bit-identical from run to run): (labels[, counts][, inertia])."""
+        N, D = self._index_rows("index_assign", "rows", rows)
+        K, _ = self._index_rows("index_assign", "centroids", centroids, D)
+        if norms.dtype != torch.float32 or norms.numel() != K or not norms.is_contiguous():
+            raise ValueError(f"index_assign: norms must be f32 [{K}]")
+        labels = torch.empty(N, device=rows.device, dtype=torch.int32)
+        counts = torch.empty(K, device=rows.device, dtype=torch.int32) if return_counts else None
+        inertia = torch.empty(1, device=rows.device, dtype=torch.float64) if return_inertia else None
+        _lib.call("svc_index_assign", self._ctx, ctypes.c_void_p(rows.data_ptr()), N, D, rows.stride(0),
+                  ctypes.c_void_p(centroids.data_ptr()), _ptr(norms), K, centroids.stride(0), _ptr(labels),
+                  _ptr(counts), _ptr(inertia), _stream())
+        out = (labels,) + ((counts,) if return_counts else ()) + ((inertia,) if return_inertia else ())
+        return out if len(out) > 1 else labels
+
+    def index_update(self, rows, labels, prev, out=None, return_counts=False):
+        """Lloyd's centroid update (svc_index_update): the exact mean of the rows f16 [N, D] of every label (int32 [N],
+        values in [0, K)), rounded once to f16; a cluster without a row keeps prev's row (f16 [K, D]). out: the
+        centroids' tensor, which may be prev itself. -> (centroids f16 [K, D], norms f32 [K][, counts int32 [K]])."""
+        N, D = self._index_rows("index_update", "rows", rows)
+        K, _ = self._index_rows("index_update", "prev", prev, D)
+        if labels.dtype != torch.int32 or labels.numel() != N or not labels.is_contiguous():
+            raise ValueError(f"index_update: labels must be int32 [{N}]")
+        if out is None:
+            out = torch.empty(K, D, device=rows.device, dtype=torch.float16)
+        elif self._index_rows("index_update", "out", out, D)[0] != K:
+            raise ValueError(f"index_update: out must be f16 [{K}, {D}]")
+        norms = torch.empty(K, device=rows.device, dtype=torch.float32)
+        counts = torch.empty(K, device=rows.device, dtype=torch.int32) if return_counts else None
+        _lib.call("svc_index_update", self._ctx, ctypes.c_void_p(rows.data_ptr()), N, D, rows.stride(0), _ptr(labels),
+                  K, ctypes.c_void_p(prev.data_ptr()), prev.stride(0), ctypes.c_void_p(out.data_ptr()), out.stride(0),
+                  _ptr(norms), _ptr(counts), _stream())
+        return (out, norms, counts) if return_counts else (out, norms)
+
+    def index_kmeans(self, rows, K, iters=10, return_labels=False):
+        """A retrieval index compacted to K centroids (svc_index_kmeans): the centroids start as rows floor(i N / K)
+        (iters = 0 returns exactly that strided sample), then `iters` rounds of index_assign + index_update, and one
+        last assignment. No early stop, no random numbers, no host synchronisation. -> (centroids f16 [K, D], norms
+        f32 [K], counts int32 [K], inertia f64 [iters + 1][, labels int32 [N]])."""
+        N, D = self._index_rows("index_kmeans", "rows", rows)
+        K, iters = int(K), int(iters)
+        if not 1 <= K <= N:
+            raise ValueError(f"index_kmeans: K={K} (1 <= K <= N={N})")
+        if not 0 <= iters <= 1000:
+            raise ValueError(f"index_kmeans: iters={iters} (0 <= iters <= 1000)")
+        cent = torch.empty(K, D, device=rows.device, dtype=torch.float16)
+        norms = torch.empty(K, device=rows.device, dtype=torch.float32)
+        counts = torch.empty(K, device=rows.device, dtype=torch.int32)
+        inertia = torch.empty(iters + 1, device=rows.device, dtype=torch.float64)
+        labels = torch.empty(N, device=rows.device, dtype=torch.int32) if return_labels else None
+        _lib.call("svc_index_kmeans", self._ctx, ctypes.c_void_p(rows.data_ptr()), N, D, rows.stride(0), K, iters,
+                  ctypes.c_void_p(cent.data_ptr()), cent.stride(0), _ptr(norms), _ptr(labels), _ptr(counts),
+                  _ptr(inertia), _stream())
+        return (cent, norms, counts, inertia, labels) if return_labels else (cent, norms, counts, inertia)
+
     def load_singer_index(self, path):
         """Replace engine.singer_index by the table saved at `path` (SingerIndexTable.save), on this engine's device;
         an index whose row width or content types differ from this configuration's content is a ValueError."""

@@ -210,10 +210,16 @@ class SVCServer:
         req.frames = self._frames(int(_lib.load().svc_resample_len(info.n_frames, info.sr, int(self._fs))))
         return req
 
-    def enroll(self, singer, sources=None, wavs24=None, max_batch=16):
+    def enroll(self, singer, sources=None, wavs24=None, max_batch=16, **index_args):
         """SVCPipeline.enroll on the server's pipeline (it takes the engine's lock, so it runs between batches): the
-        singer's F0 median from the singer's own recordings becomes the pitch target of later requests."""
-        return self.pipeline.enroll(singer, sources=sources, wavs24=wavs24, max_batch=max_batch)
+        singer's F0 median from the singer's own recordings becomes the pitch target of later requests. index_args:
+        SVCPipeline.enroll's index arguments (index, index_max_rows, index_compact, index_iters, wavs16, wavs16_float),
+        passed through as given; any other name is a TypeError."""
+        unknown = sorted(set(index_args) - {"index", "index_max_rows", "index_compact", "index_iters", "wavs16",
+                                            "wavs16_float"})
+        if unknown:
+            raise TypeError(f"enroll: unexpected argument(s) {unknown}")
+        return self.pipeline.enroll(singer, sources=sources, wavs24=wavs24, max_batch=max_batch, **index_args)
 
     def close(self, wait=True):
         """Stop accepting requests; the worker finishes every queued request first."""

@@ -81,6 +81,21 @@ def check_index_rate(index_rate):
     return float(index_rate)
 
 
+INDEX_COMPACT = ("stride", "kmeans")
+
+
+def check_index_compact(index_compact, index_iters=10):
+    """enroll's index compaction mode and k-means iteration count -> (mode, iters), else ValueError before any device
+    work: the mode is "stride" (keep rows floor(i N / M)) or "kmeans" (svc_index_kmeans' centroids); iters an int in
+    [0, 1000] (svc_index_kmeans' range), checked in both modes."""
+    if index_compact not in INDEX_COMPACT:
+        raise ValueError(f"index_compact {index_compact!r}: one of {list(INDEX_COMPACT)}")
+    ok = isinstance(index_iters, (int, np.integer)) and not isinstance(index_iters, (bool, np.bool_))
+    if not ok or not 0 <= int(index_iters) <= 1000:
+        raise ValueError(f"index_iters {index_iters!r}: an integer in [0, 1000]")
+    return index_compact, int(index_iters)
+
+
 def content_signature(cfg):
     """(D, content types) of the content buffer the configuration's conditioner reads: the types of
     cfg.mapper.content_feature in ascending name order and the sum of their widths (SVCPipeline.content)."""
@@ -92,19 +107,27 @@ def content_signature(cfg):
 class SingerIndexTable:
     """singer id (int) -> a retrieval index: {"rows": f16 [N, D] tensor of the singer's enrolled content frames,
     "norms": f32 [N] (svc_index_norms of the rows), "n_utts": int, "frames": int (content frames seen, before any
-    thinning), "content_types": list of str the rows were built from}. SVCPipeline.enroll(index=True) fills it;
-    svc_content_retrieve searches it (`index_rate=` on the conversion entry points)."""
+    thinning), "content_types": list of str the rows were built from}, and, only where k-means compacted the index
+    (enroll(index_compact="kmeans") with more frames than index_max_rows), "compact": {"method": "kmeans", "iters":
+    int, "inertia_first": float, "inertia_last": float, "dropped": int (centroids left without a row)}.
+    SVCPipeline.enroll(index=True) fills it; svc_content_retrieve searches it (`index_rate=` on the conversion entry
+    points)."""
 
     def __init__(self):
         self._e = {}
 
-    def set(self, singer, rows, norms, n_utts=0, frames=0, content_types=()):
+    def set(self, singer, rows, norms, n_utts=0, frames=0, content_types=(), compact=None):
         if rows.dim() != 2 or rows.dtype != torch.float16 or rows.shape[0] < 1:
             raise ValueError(f"singer {singer}: index rows must be f16 [N >= 1, D]")
         if norms.dtype != torch.float32 or norms.shape != (rows.shape[0],):
             raise ValueError(f"singer {singer}: norms must be f32 [{rows.shape[0]}]")
         self._e[int(singer)] = dict(rows=rows.contiguous(), norms=norms.contiguous(), n_utts=int(n_utts),
                                     frames=int(frames), content_types=[str(t) for t in content_types])
+        if compact is not None:
+            self._e[int(singer)]["compact"] = dict(
+                method=str(compact["method"]), iters=int(compact["iters"]),
+                inertia_first=float(compact["inertia_first"]), inertia_last=float(compact["inertia_last"]),
+                dropped=int(compact["dropped"]))
         return self._e[int(singer)]
 
     def get(self, singer, default=None):
@@ -130,6 +153,9 @@ class SingerIndexTable:
             arrays[f"norms_{k}"] = v["norms"].detach().cpu().numpy()
             meta[str(k)] = dict(n_utts=v["n_utts"], frames=v["frames"], content_types=v["content_types"],
                                 rows=int(v["rows"].shape[0]), dim=int(v["rows"].shape[1]))
+            if "compact" in v:  # the inertias as float.hex, so they round-trip exactly
+                meta[str(k)]["compact"] = dict(v["compact"], inertia_first=float(v["compact"]["inertia_first"]).hex(),
+                                               inertia_last=float(v["compact"]["inertia_last"]).hex())
         with open(path, "wb") as f:
             np.savez(f, meta=np.array(json.dumps({"singer_index": meta})), **arrays)
 
@@ -153,5 +179,8 @@ class SingerIndexTable:
                                      f"configuration uses {list(content_types)}")
                 t.set(int(k), torch.from_numpy(rows.view(np.int16)).view(torch.float16).to(device),
                       torch.from_numpy(np.ascontiguousarray(doc[f"norms_{k}"], np.float32)).to(device), m["n_utts"],
-                      m["frames"], m["content_types"])
+                      m["frames"], m["content_types"],
+                      compact=None if "compact" not in m else dict(
+                          m["compact"], inertia_first=float.fromhex(m["compact"]["inertia_first"]),
+                          inertia_last=float.fromhex(m["compact"]["inertia_last"])))
         return t
