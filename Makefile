@@ -40,6 +40,13 @@ build/loudness.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include
 	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
 	@python3 tools/check_kernel_resources.py build/$*.res 'loudness_(power|apply)_kernel' 128 || { rm -f $@; exit 1; }
 
+# the join of long-form conversion: stitch_seams runs a song's seams on one workgroup of up to 1024 threads (128
+# registers each) with two f64 sums per candidate; a spill would put its inner loop on scratch
+build/stitch.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include/svc_hip.h
+	@mkdir -p build
+	$(HIPCC) $(CXXFLAGS) -c $< -o $@ -Rpass-analysis=kernel-resource-usage 2> build/$*.res || { cat build/$*.res; rm -f $@; exit 1; }
+	@python3 tools/check_kernel_resources.py build/$*.res 'stitch_(seams|write)_kernel' 128 || { rm -f $@; exit 1; }
+
 # feature retrieval: knn_topk keeps 64 accumulator and 32 top-k registers per lane and indexes both statically; a spill
 # would put the selection epilogue on scratch
 build/retrieve.o: build/%.o: $(SRC_DIR)/%.hip $(wildcard $(SRC_DIR)/*.h) include/svc_hip.h

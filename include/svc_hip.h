@@ -34,6 +34,9 @@
  *                          itself is written on the host)
  *   svc_loudness_match  <- no counterpart in the reference: so-vits-svc's loudness envelope adjustment, between
  *                          svc_bigvgan and svc_pcm16 (the output takes the source's slow RMS envelope)
+ *   svc_stitch          <- no counterpart in the reference: so-vits-svc's --clip crossfade with RVC's SOLA alignment,
+ *                          between svc_bigvgan and svc_loudness_match (overlapping chunks of a long clip, converted
+ *                          as separate utterances, joined into one waveform)
  *   svc_content_retrieve <- no counterpart in the reference: RVC's feature index (index_rate), between the content
  *                          stage and svc_condition (each content frame blended with its k nearest frames of the
  *                          target singer's own recordings; svc_index_norms prepares an index)
@@ -451,6 +454,43 @@ int64_t svc_loudness_frames(int64_t n_out, int hop);
 svc_status svc_loudness_match(svc_ctx* ctx, const float* wav, const float* src, int B, int64_t S, int64_t S_src,
                               const int64_t* utt_samples, const int64_t* src_samples, int window, int hop, double mix,
                               double floor_rms, double max_gain, float* out, double* gain_out, void* stream);
+
+/* Long-form conversion's join (opt-in, after svc_bigvgan): B chunks, each the waveform of one utterance, are written
+   into `out`; a chunk that continues its predecessor is aligned to it by SOLA and crossfaded over X = xfade samples,
+   with candidates d in [-R, R), R = search (d = 0 alone when R = 0). All tables are host arrays of length B:
+     rows[b]     device pointer of chunk b's waveform, n[b] usable samples (pointers into the vocoder's output as it
+                 stands; nothing is copied)
+     lead[b]     the row index of chunk b's first body sample; body[b] its body samples
+     joined[b]   1: chunk b continues chunk b - 1 of the same song, else 0; joined[0] = 0
+     out_off[b]  the index in out of chunk b's first body sample
+   Every chunk has a displacement d_b, 0 for an unjoined chunk, and plays row sample lead[b] + d_b + j at
+   out[out_off[b] + j], j < body[b]. For a joined chunk b:
+     a_j = rows[b-1][lead[b-1] + d_{b-1} + body[b-1] + j], j < X: the predecessor as it was actually played, so the
+     seams of a song form a chain; c_j(d) = rows[b][lead[b] + d + j];
+     nom(d) = sum_j (double)a_j (double)c_j(d), den(d) = sum_j (double)c_j(d)^2, in f64 with j ascending from 0 (each
+     product is exact in f64, so fused and unfused multiply-adds give the same sums);
+     q(d) = nom |nom| / (den + eps), three IEEE f64 operations: it orders the candidates as SOLA's nom / sqrt(den + eps);
+     d_b = the candidate first by greater q, then smaller |d|, then greater d (silence gives 0);
+     out[out_off[b] + j] = (float)(a_j + w_j (c_j(d_b) - a_j)), w_j = (j + 0.5) / X in f64, for j < X; for
+     X <= j < body[b], and for the whole body of an unjoined chunk, the row sample is copied bit for bit.
+   This is audio.stitch, the project's host definition: displacements and q bit-equal, crossfade samples within 1 f32
+   ulp. shift_out: optional device int32 [B], d_b. q_out: optional device f64 [B][max(2R, 1)], q(d) at index d + R, 0
+   for an unjoined chunk. Exactly the intervals [out_off[b], out_off[b] + body[b]) of out are written.
+   Two launches whatever B is: stitch_seams (one workgroup per song walks its seams in order: both windows in LDS, one
+   candidate per thread, a workgroup arg-max) and stitch_write (chunks x blocks of output samples). Songs run in
+   parallel. All buffers need 4-byte alignment only (q_out 8). The context need not be finalized; the tables go through
+   a ring of this entry point's own, so the call may run on any stream.
+   SVC_ERR_INVALID before any HIP call: null ctx, rows, a row pointer, a table or out; B < 1; xfade outside [1, 8192];
+   search outside [0, 1024]; eps not > 0; out_len < 1; joined[0] != 0 or a joined[b] other than 0 / 1; for a joined b,
+   out_off[b] != out_off[b-1] + body[b-1] or body[b] < xfade; a body[b] < 1 or n[b] < 1; an output interval outside
+   [0, out_len); two output intervals that overlap; out overlapping a row; any row index that the definitions can
+   read, for any admissible displacement of chunk b and of its predecessor, outside [0, n[b]): that is
+   lead[b] - (joined[b] ? R : 0) < 0, or lead[b] + (joined[b] && R ? R - 1 : 0) + body[b] + (joined[b+1] ? X : 0) > n[b].
+   Non-finite samples are the caller's error: they give undefined displacements and samples, never an access outside
+   the buffers. */
+svc_status svc_stitch(svc_ctx* ctx, const float* const* rows, int B, const int64_t* n, const int64_t* lead,
+                      const int64_t* body, const int32_t* joined, const int64_t* out_off, int xfade, int search,
+                      double eps, float* out, int64_t out_len, int32_t* shift_out, double* q_out, void* stream);
 
 /* Feature retrieval, part 1: the squared norms of an index. index16: binary16 [N] rows of ld >= D halves (a singer's
    enrolled content frames). norms[j] = (float) sum_c (double)x[j][c]^2 over the row's D values in column order (every

@@ -65,6 +65,8 @@ PROTOTYPES = {
     "svc_loudness_frames": (c_int64, [c_int64, c_int]),
     "svc_loudness_match": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int,
                                    c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "svc_stitch": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                           c_double, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "svc_index_norms": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
     "svc_content_retrieve": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                      c_void_p, c_int64, c_int, c_int, c_double, c_double, c_void_p, c_int, c_void_p,

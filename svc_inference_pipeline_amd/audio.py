@@ -17,6 +17,7 @@ librosa.load).
 """
 import collections
 import ctypes
+import fractions
 import math
 import os
 import struct
@@ -306,6 +307,203 @@ def loudness_match(y, x, fs=None, window=None, hop=None, mix=0.0, floor_rms=1e-6
     frac = (i - k0 * hop).astype(np.float64) / float(hop)
     k1 = np.minimum(k0 + 1, len(g) - 1)
     return (y.astype(np.float64) * (g[k0] + frac * (g[k1] - g[k0]))).astype(np.float32)
+
+
+CHUNK_GRID = 15          # mel frames: 3840 samples at 24 kHz = 2560 at 16 kHz = 8 Whisper or HuBERT frames
+VOCODER_FADE_FRAMES = 20  # the vocoder fades out the last 20 * hop samples of every utterance (runtime: vocoder.fade_out)
+MAX_CHUNKS = 1 << 12      # chunk k of utterance u draws its noise as utterance (u << 12) | k, an int32 id
+STITCH_EPS = 1e-8         # RVC's SOLA: nom / sqrt(den + 1e-8)
+
+# The join's tables (svc_stitch's arguments; all in samples): chunk b has n[b] usable samples, its body is
+# row[lead[b] : lead[b] + body[b]] before displacement and lands at out[out_off[b] : out_off[b] + body[b]]
+StitchPlan = collections.namedtuple("StitchPlan", "n lead body joined out_off out_len xfade search eps")
+
+# One song cut into chunks (chunk_plan). Per chunk, lists of length `chunks`: start / frames (its first source frame and
+# its own frame count T_k), body (frames [b0, b1) of the song it is responsible for), rows24 / rows16 / rows16_float
+# (the sample intervals [lo, hi) of the source signals it is converted from), noise_ids; stitch: its StitchPlan, with
+# out_off relative to the song's first sample and out_len = T_song * hop
+ChunkPlan = collections.namedtuple("ChunkPlan", "T_song hop Cb Lc Rc chunks start frames body rows24 rows16 "
+                                                "rows16_float noise_ids stitch")
+
+
+def chunk_plan(n_samples, fs=24000, hop=256, n_fft=1024, clip_s=10.0, context_s=0.64, xfade=1024, search=192,
+               utt_id=0, n16=None, n16_float=None, eps=STITCH_EPS):
+    """The chunks of a song of n_samples 24 kHz samples for long-form conversion (DESIGN.md "Long-form conversion") ->
+    ChunkPlan. In mel frames, all multiples of 15 (CHUNK_GRID: a whole sample at 24 and 16 kHz and a whole frame of both
+    content encoders): the body length Cb = clip_s * fs / hop rounded down (at least 15), the contexts Lc = Rc =
+    context_s * fs / hop rounded up. A cut lies at frame k Cb, k >= 1, while k Cb + Rc < T_song; chunk k is converted
+    from source frames [max(0, k Cb - Lc), (k + 1) Cb + Rc) (the last chunk: to the song's last sample) and is
+    responsible for frames [k Cb, (k + 1) Cb) (the last chunk: to T_song). Its 16 kHz rows are the same interval times
+    2 / 3, clipped to that signal's length (n16, n16_float; default: n_samples * 2 // 3 and none).
+    The stitch tables: a chunk with a successor has n = T_k hop - 20 hop usable samples (the vocoder fades out the
+    rest), the last chunk T_k hop. A joined last chunk can be displaced by up to search - 1 samples towards its end,
+    where there is nothing left to play: its stitched body is that much shorter, and the song's last
+    max(search - 1, 0) samples, the silent end of the vocoder's fade-out, stay zero.
+    ValueError: Rc hop < xfade + search + 20 hop, Lc hop < search, xfade > 15 hop, xfade or search outside
+    svc_stitch's ranges, more than 4096 chunks, utt_id outside [0, 2^19), a song of less than one frame."""
+    from .runtime import mel_frames
+    n_samples, fs, hop, xfade, search, utt_id = int(n_samples), int(fs), int(hop), int(xfade), int(search), int(utt_id)
+    G = CHUNK_GRID
+    if not clip_s > 0 or not context_s >= 0:
+        raise ValueError(f"chunk_plan: clip_s {clip_s!r} must be positive and context_s {context_s!r} not negative")
+    # the seconds as the short decimals they were written as (0.64 is 16 / 25, not the binary fraction next to it)
+    sec = lambda v: fractions.Fraction(v).limit_denominator(1000000)
+    Cb = max(math.floor(sec(clip_s) * fs / hop) // G * G, G)
+    Lc = Rc = -(-math.ceil(sec(context_s) * fs / hop) // G) * G
+    if not 1 <= xfade <= 8192 or not 0 <= search <= 1024:
+        raise ValueError(f"chunk_plan: xfade {xfade} (1..8192), search {search} (0..1024)")
+    if Rc * hop < xfade + search + VOCODER_FADE_FRAMES * hop:
+        raise ValueError(f"chunk_plan: right context of {Rc * hop} samples is shorter than xfade + search + the "
+                         f"vocoder's fade-out ({xfade} + {search} + {VOCODER_FADE_FRAMES * hop})")
+    if Lc * hop < search:
+        raise ValueError(f"chunk_plan: left context of {Lc * hop} samples is shorter than search {search}")
+    if xfade > G * hop:
+        raise ValueError(f"chunk_plan: xfade {xfade} is longer than the shortest body ({G * hop} samples)")
+    if not 0 <= utt_id < (1 << 19):
+        raise ValueError(f"chunk_plan: utterance id {utt_id} outside [0, 2^19): chunk noise ids are (id << 12) | k")
+    T_song = mel_frames(n_samples, n_fft, hop)
+    if T_song < 1:
+        raise ValueError(f"chunk_plan: {n_samples} samples are less than one frame")
+    K = 1
+    while K * Cb + Rc < T_song:
+        K += 1
+        if K > MAX_CHUNKS:
+            raise ValueError(f"chunk_plan: more than {MAX_CHUNKS} chunks of {Cb} frames in {T_song} frames")
+    n16 = n_samples * 2 // 3 if n16 is None else int(n16)
+    start, frames, body, rows24, rows16, rows16f = [], [], [], [], [], []
+    sn, lead, sbody, joined, out_off = [], [], [], [], []
+    for k in range(K):
+        last = k == K - 1
+        s = max(0, k * Cb - Lc)
+        e = T_song if last else (k + 1) * Cb + Rc
+        b0, b1 = k * Cb, (T_song if last else (k + 1) * Cb)
+        lo, hi = s * hop, (n_samples if last else e * hop)
+        start.append(s), frames.append(e - s), body.append((b0, b1)), rows24.append((lo, hi))
+        lo16, hi16 = lo * 2 // 3, hi * 2 // 3
+        rows16.append((min(lo16, n16), n16 if last else min(hi16, n16)))
+        if n16_float is not None:
+            rows16f.append((min(lo16, int(n16_float)), int(n16_float) if last else min(hi16, int(n16_float))))
+        sn.append((e - s) * hop - (0 if last else VOCODER_FADE_FRAMES * hop))
+        lead.append((b0 - s) * hop)
+        sbody.append((b1 - b0) * hop - (max(search - 1, 0) if last and k > 0 else 0))
+        joined.append(1 if k > 0 else 0)
+        out_off.append(b0 * hop)
+    for k in range(K):  # svc_stitch's range rule, whatever the contexts were clipped to
+        d_lo, d_hi = (-search, max(search - 1, 0)) if joined[k] else (0, 0)
+        tail = xfade if k + 1 < K else 0
+        if lead[k] + d_lo < 0 or lead[k] + d_hi + sbody[k] + tail > sn[k] or (joined[k] and sbody[k] < xfade):
+            raise ValueError(f"chunk_plan: chunk {k} of {K}: rows [{lead[k] + d_lo}, {lead[k] + d_hi + sbody[k] + tail}) "
+                             f"of {sn[k]} usable samples")
+    st = StitchPlan(sn, lead, sbody, joined, out_off, T_song * hop, xfade, search, float(eps))
+    return ChunkPlan(T_song, hop, Cb, Lc, Rc, K, start, frames, body, rows24, rows16,
+                     rows16f if n16_float is not None else None, [(utt_id << 12) | k for k in range(K)], st)
+
+
+def merge_stitch_plans(plans, out_stride):
+    """The StitchPlans of several songs (equal xfade, search, eps) as one: song i's out_off moved by i * out_stride."""
+    p0 = plans[0]
+    if any((p.xfade, p.search, p.eps) != (p0.xfade, p0.search, p0.eps) for p in plans):
+        raise ValueError("merge_stitch_plans: the songs' xfade, search and eps differ")
+    if any(p.out_len > out_stride for p in plans):
+        raise ValueError("merge_stitch_plans: a song is longer than out_stride")
+    cat = lambda f: [v for p in plans for v in getattr(p, f)]
+    off = [v + i * int(out_stride) for i, p in enumerate(plans) for v in p.out_off]
+    return StitchPlan(cat("n"), cat("lead"), cat("body"), cat("joined"), off, len(plans) * int(out_stride), p0.xfade,
+                      p0.search, p0.eps)
+
+
+def check_stitch_plan(plan, rows_len=None):
+    """svc_stitch's argument rules on a StitchPlan (ValueError); rows_len: the rows' allocated lengths, each >= n[b]."""
+    B = len(plan.n)
+    X, R = int(plan.xfade), int(plan.search)
+    if B < 1 or any(len(t) != B for t in (plan.lead, plan.body, plan.joined, plan.out_off)):
+        raise ValueError("stitch: the tables need one entry per chunk, at least one chunk")
+    if not 1 <= X <= 8192 or not 0 <= R <= 1024 or not plan.eps > 0 or plan.out_len < 1:
+        raise ValueError(f"stitch: xfade {X} (1..8192), search {R} (0..1024), eps {plan.eps} (> 0), out_len {plan.out_len}")
+    if plan.joined[0]:
+        raise ValueError("stitch: chunk 0 is joined to a predecessor it does not have")
+    for b in range(B):
+        n, lead, body, j, off = plan.n[b], plan.lead[b], plan.body[b], plan.joined[b], plan.out_off[b]
+        if j not in (0, 1) or n < 1 or body < 1 or off < 0 or off + body > plan.out_len:
+            raise ValueError(f"stitch: chunk {b}: joined {j}, n {n}, body {body}, output [{off}, {off + body}) of "
+                             f"{plan.out_len}")
+        if rows_len is not None and rows_len[b] < n:
+            raise ValueError(f"stitch: chunk {b}: a row of {rows_len[b]} samples, n {n}")
+        if j and (off != plan.out_off[b - 1] + plan.body[b - 1] or body < X):
+            raise ValueError(f"stitch: chunk {b} is joined: its output must start where chunk {b - 1}'s ends, and its "
+                             f"body {body} must hold xfade {X}")
+        d_lo, d_hi = (-R, max(R - 1, 0)) if j else (0, 0)
+        tail = X if b + 1 < B and plan.joined[b + 1] else 0
+        if lead < 0 or lead + d_lo < 0 or lead + d_hi + body + tail > n:
+            raise ValueError(f"stitch: chunk {b}: rows [{lead + d_lo}, {lead + d_hi + body + tail}) are read, the row "
+                             f"has [0, {n})")
+    order = sorted(range(B), key=lambda b: plan.out_off[b])
+    for x, y in zip(order, order[1:]):
+        if plan.out_off[x] + plan.body[x] > plan.out_off[y]:
+            raise ValueError(f"stitch: the output intervals of chunks {x} and {y} overlap")
+
+
+def stitch_q(a, row, lead, xfade, search, eps):
+    """q(d) of every candidate d in [-search, search) (d = 0 alone for search 0), f64 [max(2 search, 1)]: a f32
+    [xfade] is the predecessor's continuation, the candidates' windows are row[lead + d : lead + d + xfade]. The sums
+    run in f64 with j ascending (np.cumsum adds in order; pairwise np.sum would not)."""
+    X, R = int(xfade), int(search)
+    nc = max(2 * R, 1)
+    a = np.asarray(a, dtype=np.float32).astype(np.float64)
+    seg = np.asarray(row[lead - R:lead - R + X + nc - 1], dtype=np.float32).astype(np.float64)
+    win = np.lib.stride_tricks.sliding_window_view(seg, X)  # [nc, X]: row k is candidate d = k - R
+    nom = np.cumsum(win * a[None, :], axis=1)[:, -1]
+    den = np.cumsum(win * win, axis=1)[:, -1]
+    return (nom * np.abs(nom)) / (den + np.float64(eps))
+
+
+def stitch_pick(q, search):
+    """The displacement among candidates d = k - search (k indexes q): greater q, then smaller |d|, then greater d."""
+    best_q, best_d = None, 0
+    for k, qk in enumerate(q.tolist()):
+        d = k - int(search)
+        if best_q is None or qk > best_q or (qk == best_q and (abs(d) < abs(best_d) or (abs(d) == abs(best_d) and d > best_d))):
+            best_q, best_d = qk, d
+    return best_d
+
+
+def stitch(rows, plan, return_shifts=False, return_q=False, chain=True):
+    """Join converted chunks into their songs (DESIGN.md "Long-form conversion"); the definition svc_stitch is tested
+    against, f64 inside. rows: B f32 arrays, chunk b's waveform with at least plan.n[b] samples; plan: a StitchPlan
+    -> out f32 [plan.out_len], zeros wherever no body lands. With X = xfade, R = search and d_b the displacement of
+    chunk b (0 unless joined), chunk b plays row sample lead[b] + d_b + j at out[out_off[b] + j], j < body[b]. A
+    joined chunk b: its predecessor, as it was actually played, continues as a_j = rows[b-1][lead[b-1] + d_{b-1} +
+    body[b-1] + j], j < X (so a song's seams form a chain); d_b is the candidate in [-R, R) first by greater
+    q(d) = nom |nom| / (den + eps), then smaller |d|, then greater d, where nom = sum a_j c_j(d), den = sum c_j(d)^2,
+    c_j(d) = rows[b][lead[b] + d + j], summed in f64 in ascending j (SOLA's nom / sqrt(den + eps) ordering without the
+    root); its first X samples are f32(a_j + w_j (c_j(d_b) - a_j)), w_j = (j + 0.5) / X; everything else is copied bit
+    for bit. return_shifts: also the displacements int32 [B]; return_q: also q f64 [B, max(2R, 1)] (0 for unjoined
+    chunks). chain=False takes d_{b-1} as 0 in a_j (what a stitch without the chain would do: tests only)."""
+    B = len(plan.n)
+    rows = [np.asarray(r, dtype=np.float32).reshape(-1) for r in rows]
+    if len(rows) != B:
+        raise ValueError(f"stitch: {len(rows)} rows for {B} chunks")
+    check_stitch_plan(plan, [len(r) for r in rows])
+    X, R = int(plan.xfade), int(plan.search)
+    out = np.zeros(int(plan.out_len), dtype=np.float32)
+    shifts = np.zeros(B, dtype=np.int32)
+    qs = np.zeros((B, max(2 * R, 1)), dtype=np.float64)
+    for b in range(B):
+        lead, body, off = int(plan.lead[b]), int(plan.body[b]), int(plan.out_off[b])
+        if not plan.joined[b]:
+            out[off:off + body] = rows[b][lead:lead + body]
+            continue
+        pa = int(plan.lead[b - 1]) + (int(shifts[b - 1]) if chain else 0) + int(plan.body[b - 1])
+        a = rows[b - 1][pa:pa + X]
+        qs[b] = stitch_q(a, rows[b], lead, X, R, plan.eps)
+        d = shifts[b] = stitch_pick(qs[b], R)
+        c = rows[b][lead + d:lead + d + body]
+        out[off:off + body] = c
+        a64, c64 = a.astype(np.float64), c[:X].astype(np.float64)
+        w = (np.arange(X, dtype=np.float64) + 0.5) / np.float64(X)
+        out[off:off + X] = (a64 + w * (c64 - a64)).astype(np.float32)
+    res = (out,) + ((shifts,) if return_shifts else ()) + ((qs,) if return_q else ())
+    return res if len(res) > 1 else out
 
 
 def write_wav_pcm16(path, pcm, fs):

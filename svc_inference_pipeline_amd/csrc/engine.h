@@ -134,6 +134,7 @@ struct svc_ctx {
   StageRing lens_feat, lens_main;
   StageRing lens_pcm;  // svc_pcm16: the length table and, behind it in the same slot, the zeroed peak scratch
   StageRing lens_loud;  // svc_loudness_match: the two length tables and, behind them in the same slot, the frame powers
+  StageRing lens_stitch;  // svc_stitch: the chunk and song tables and, behind them in the same slot, the displacements
   StageRing lens_retr;  // svc_content_retrieve: the frames and sel tables
   StageRing lens_load;  // svc_load_pcm: the utterance and plan tables and the zeroed peak scratch (load_pcm.hip)
   std::map<std::string, Param> params;

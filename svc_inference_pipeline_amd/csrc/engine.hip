@@ -273,6 +273,7 @@ svc_status svc_ctx_destroy(svc_ctx* c) {
   c->lens_main.release();
   c->lens_pcm.release();
   c->lens_loud.release();
+  c->lens_stitch.release();
   c->lens_retr.release();
   c->lens_load.release();
   delete c;

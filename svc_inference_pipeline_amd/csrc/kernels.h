@@ -102,6 +102,10 @@ size_t loudness_power_bytes(int B, int64_t K_max);
 int loudness_match(const float* wav, const float* src, int B, int64_t S, int64_t S_src, void* table, int64_t K_max,
                    int window, int hop, double mix, double floor_rms, double max_gain, float* out, double* gain_out,
                    int64_t K_out, hipStream_t s);
+// stitch.hip: the host half of svc_stitch (checks, the staged table, two launches)
+int stitch(StageRing* ring, const int* device, const float* const* rows, int B, const int64_t* n, const int64_t* lead,
+           const int64_t* body, const int32_t* joined, const int64_t* out_off, int xfade, int search, double eps,
+           float* out, int64_t out_len, int32_t* shift_out, double* q_out, hipStream_t s);
 // retrieve.hip: feature retrieval. table (device): int32 frames[B], then int32 sel[B]
 int index_norms(const f16* x, int64_t N, int D, int ld, float* norms, hipStream_t s);
 int retrieve_splits(int M, int64_t N);

@@ -25,25 +25,6 @@ constexpr int kSpan = 2048;  // samples of one clip per apply block: two 16-byte
 // case, kSpan + 1 (for any H it is at most (kSpan - 2) / H + 3)
 constexpr int kGainsMax = kSpan + 2;
 
-// x[0..3] = row[i0 .. i0 + 4), all four inside [0, n). One 16-byte load where the address is aligned, else the two
-// aligned quads that cover the four samples where both lie inside [0, n), else four 4-byte loads.
-__device__ __forceinline__ void load4(const float* row, int64_t i0, int64_t n, float* x) {
-  const int mis = (int)((reinterpret_cast<uintptr_t>(row + i0) >> 2) & 3);
-  if (mis == 0) {
-    const float4 p = *reinterpret_cast<const float4*>(row + i0);
-    x[0] = p.x, x[1] = p.y, x[2] = p.z, x[3] = p.w;
-  } else if (i0 - mis >= 0 && i0 - mis + 8 <= n) {
-    const float4* a = reinterpret_cast<const float4*>(row + i0 - mis);
-    const float4 p = a[0], q = a[1];
-    if (mis == 1) x[0] = p.y, x[1] = p.z, x[2] = p.w, x[3] = q.x;
-    else if (mis == 2) x[0] = p.z, x[1] = p.w, x[2] = q.x, x[3] = q.y;
-    else x[0] = p.w, x[1] = q.x, x[2] = q.y, x[3] = q.z;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) x[k] = row[i0 + k];
-  }
-}
-
 // power[(sig * B + b) * K_max + k] = P_k of signal sig (0: the source, 1: the output) of clip b, 0 for k >= K_b.
 // One block per (k, b, sig). The frame's samples inside the signal are [lo, hi); thread t adds, in ascending order, the
 // squares of samples lo + 4 q .. lo + 4 q + 3 for q = t, t + 256, ...; then the 64-lane butterfly, then the four waves'

@@ -1,5 +1,5 @@
 // Device primitives shared by the hand-written kernels: LDS-DMA, buffer descriptors, counted waits, workgroup barriers,
-// the XCD remap, the 128-B-row swizzle, the 4 x f16 pack and the 64-lane butterflies. One definition each, with its
+// the XCD remap, the 128-B-row swizzle, the 4 x f16 pack, the 16-byte load of an f32 row and the 64-lane butterflies. One definition each, with its
 // hazard note; a kernel file keeps only the helpers that encode its own schedule or LDS layout. Everything here is
 // __forceinline__: moving a kernel onto one of these must leave its device assembly unchanged (`make isa`).
 #pragma once
@@ -102,6 +102,26 @@ __device__ __forceinline__ int xcd_remap() {
 // involution), which makes the ds_read_b128 fragment reads (16 consecutive rows per lane group) conflict-free for every
 // starting row.
 __device__ __forceinline__ int sw128(int row, int kv) { return kv ^ (row & 6); }
+
+// ------------------------------------------------------------------------------------- unaligned f32 rows, 16 B at a time
+// x[0..3] = row[i0 .. i0 + 4), all four inside [0, n). One 16-byte load where the address is aligned, else the two
+// aligned quads that cover the four samples where both lie inside [0, n), else four 4-byte loads.
+__device__ __forceinline__ void load4(const float* row, int64_t i0, int64_t n, float* x) {
+  const int mis = (int)((reinterpret_cast<uintptr_t>(row + i0) >> 2) & 3);
+  if (mis == 0) {
+    const float4 p = *reinterpret_cast<const float4*>(row + i0);
+    x[0] = p.x, x[1] = p.y, x[2] = p.z, x[3] = p.w;
+  } else if (i0 - mis >= 0 && i0 - mis + 8 <= n) {
+    const float4* a = reinterpret_cast<const float4*>(row + i0 - mis);
+    const float4 p = a[0], q = a[1];
+    if (mis == 1) x[0] = p.y, x[1] = p.z, x[2] = p.w, x[3] = q.x;
+    else if (mis == 2) x[0] = p.z, x[1] = p.w, x[2] = q.x, x[3] = q.y;
+    else x[0] = p.w, x[1] = q.x, x[2] = q.y, x[3] = q.z;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = row[i0 + k];
+  }
+}
 
 // ---------------------------------------------------------------------------------------------- 64-lane butterflies
 // Every lane of the wave gets the result; all 64 lanes must be active. (T: int, float or double. No wave_min: the one

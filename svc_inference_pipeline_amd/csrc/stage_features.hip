@@ -352,6 +352,16 @@ svc_status svc_loudness_match(svc_ctx* c, const float* wav, const float* src, in
                         1 + S / hop, s);
 }
 
+// ---------------------------------------------------------------------------- long-form conversion: the join
+svc_status svc_stitch(svc_ctx* c, const float* const* rows, int B, const int64_t* n, const int64_t* lead,
+                      const int64_t* body, const int32_t* joined, const int64_t* out_off, int xfade, int search,
+                      double eps, float* out, int64_t out_len, int32_t* shift_out, double* q_out, void* stream) {
+  SVC_REQUIRE(c, "stitch: null context");
+  // the context is read only once the arguments have passed (stitch.hip checks them before any HIP call)
+  return stitch(&c->lens_stitch, &c->device, rows, B, n, lead, body, joined, out_off, xfade, search, eps, out, out_len,
+                shift_out, q_out, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------- wav payloads -> the input batches (A1)
 svc_status svc_load_pcm(svc_ctx* c, const void* raw, int B, const int64_t* byte_off, const int64_t* n_frames,
                         const int32_t* format, const int32_t* channels, const int32_t* sr_in, int sr_src,

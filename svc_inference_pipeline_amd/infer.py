@@ -8,6 +8,7 @@ converted wav, on one MI355X through libsvc_hip.so.
         # measure the singer's voiced F0 median from the singer's own recordings and keep it in f0.json
     python -m svc_inference_pipeline_amd.infer --singer-f0 f0.json --key 2 --wav a.wav ...   # use it; 2 semitones up
     python -m svc_inference_pipeline_amd.infer --k-step 300 --fast --wav a.wav ...   # shallow diffusion from step 300
+    python -m svc_inference_pipeline_amd.infer --clip 10 --fast --wav song.wav ...   # a long file in 10 s chunks
     python -m svc_inference_pipeline_amd.infer --resynth --vocoder-ckpt vocoder.pt --wav a.wav   # vocoder only
 
 Same sequence as the reference: acoustic features (mel, energy, Praat F0) -> pitch shift to the target
@@ -126,10 +127,12 @@ def convert_file(engine, cfg, wav_path, singer_name, fast_inference=False, speed
 
 def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, speedup=10, seed=0, device="cuda",
                   f0_method="parselmouth", pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source",
-                  loudness_mix=None, solver=None, solver_steps=20, index_rate=None):
+                  loudness_mix=None, solver=None, solver_steps=20, index_rate=None, clip_s=None, context_s=0.64):
     """Several files as ONE ragged batch (SVCPipeline.convert_many, per-utterance lengths through the C-ABI) ->
     list of (f32 waveform [T_i*hop], T_i); file i uses utterance id i, so file 0 equals convert_file's result.
-    pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform."""
+    pcm16=True: save_audio's int16 samples [T_i*hop + 2*(fs//20)] instead of each f32 waveform.
+    clip_s (--clip; None: each file is one utterance): the files are converted in overlapping chunks of clip_s seconds
+    with context_s seconds of context and stitched (SVCPipeline.convert_long)."""
     singers = C.load_singers(cfg)
     if singer_name not in singers:
         raise KeyError(f"unknown singer {singer_name!r}; known: {sorted(singers)}")
@@ -139,13 +142,16 @@ def convert_files(engine, cfg, wav_paths, singer_name, fast_inference=False, spe
     else:
         w24, w16 = A.load_batch(list(wav_paths), cfg.fs, engine)
     sid = int(singers[singer_name])
-    wavs = SVCPipeline(engine, f0_method=f0_method).convert_many(w24, w16, [sid] * len(w24), wavs16_float=w16f,
-                                            fast_inference=fast_inference, speedup=speedup, seed=seed, pcm16=pcm16,
-                                            key_shift=key_shift, **({} if k_step is None else dict(k_step=k_step)),
-                                            **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
-                                            **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
-                                            **({} if index_rate is None else dict(index_rate=index_rate)),
-                                            **({} if solver is None else dict(solver=solver, solver_steps=solver_steps)))
+    pipe = SVCPipeline(engine, f0_method=f0_method)
+    call = pipe.convert_many if clip_s is None else pipe.convert_long
+    long_kw = {} if clip_s is None else dict(clip_s=clip_s, context_s=context_s)
+    wavs = call(w24, w16, [sid] * len(w24), wavs16_float=w16f, **long_kw, fast_inference=fast_inference,
+                speedup=speedup, seed=seed, pcm16=pcm16, key_shift=key_shift,
+                **({} if k_step is None else dict(k_step=k_step)),
+                **({} if k_step_mel == "source" else dict(k_step_mel=k_step_mel)),
+                **({} if loudness_mix is None else dict(loudness_mix=loudness_mix)),
+                **({} if index_rate is None else dict(index_rate=index_rate)),
+                **({} if solver is None else dict(solver=solver, solver_steps=solver_steps)))
     hop = cfg.hop_length
     sil2 = 2 * (cfg.fs // 20) if pcm16 else 0
     return [(w.cpu().numpy(), (int(w.shape[0]) - sil2) // hop) for w in wavs]
@@ -187,6 +193,13 @@ def build_parser():
     ap.add_argument("--loudness-mix", type=float, default=None, metavar="X",
                     help="loudness envelope transfer: the converted voice takes the source's slow RMS envelope; 0 "
                          "gives it the source's envelope, 1 leaves it unchanged (default: the step is not run)")
+    ap.add_argument("--clip", type=float, default=None, metavar="SECONDS",
+                    help="long-form conversion: each file is cut into overlapping chunks of this many seconds, the "
+                         "chunks are converted as one ragged batch with the file's own F0 and key, then aligned (SOLA) "
+                         "and crossfaded back together on the GPU; memory no longer grows with the file's length "
+                         "(default: a file is one utterance)")
+    ap.add_argument("--clip-context", type=float, default=None, metavar="SECONDS",
+                    help="with --clip: the context converted on each side of a chunk (default 0.64)")
     ap.add_argument("--index", action="store_true",
                     help="with --enroll: also build the singer's retrieval index from the content frames of the "
                          "recordings (needs --singer-index to keep it)")
@@ -280,6 +293,14 @@ def main(argv=None):
         check_index_rate(args.index_rate)
     except ValueError as exc:
         ap.error(f"--index-rate: {exc}")
+    if args.clip_context is not None and args.clip is None:
+        ap.error("--clip-context needs --clip")
+    if args.clip is not None:
+        try:
+            A.chunk_plan(cfg.fs, cfg.fs, cfg.hop_length, cfg.n_fft, args.clip,
+                         0.64 if args.clip_context is None else args.clip_context)
+        except ValueError as exc:
+            ap.error(f"--clip / --clip-context: {exc}")
     if args.index and not args.enroll:
         ap.error("--index needs --enroll")
     for flag, val in (("--index-max-rows", args.index_max_rows), ("--index-compact", args.index_compact),
@@ -319,7 +340,7 @@ def main(argv=None):
     t0 = time.time()
     print("Converting...", flush=True)
     dev = f"cuda:{args.device}"
-    if len(args.wav) == 1:
+    if len(args.wav) == 1 and args.clip is None:
         results = [convert_file(engine, cfg, args.wav[0], args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
                                 k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix, solver=args.solver,
@@ -328,7 +349,9 @@ def main(argv=None):
         results = convert_files(engine, cfg, args.wav, args.singer, args.fast, args.speedup, args.seed, device=dev,
                                 f0_method=args.f0_method, pcm16=True, key_shift=args.key, k_step=args.k_step,
                                 k_step_mel=args.k_step_mel, loudness_mix=args.loudness_mix, solver=args.solver,
-                                solver_steps=args.solver_steps, index_rate=args.index_rate)
+                                solver_steps=args.solver_steps, index_rate=args.index_rate,
+                                **({} if args.clip is None else dict(
+                                    clip_s=args.clip, context_s=0.64 if args.clip_context is None else args.clip_context)))
     print(f"Using time: {time.time() - t0:.3f}s ({sum(T for _, T in results)} frames, {len(results)} file(s))",
           flush=True)
     for path, (pcm, _) in zip(args.wav, results):  # save_audio's samples, already converted on the GPU

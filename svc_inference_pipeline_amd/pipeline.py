@@ -22,7 +22,9 @@ the 15:8 map stays integral and every window starts on a mel frame). Each window
 zero-padded 30 s context and mapped with the reference's own 15:8 rule. Parity for such clips is per
 window (tests/test_gpu_long.py). Mel, F0, the sampler and BigVGAN run over the whole length in one pass:
 a 180 s song needs ~0.4 GB per vocoder stage buffer, far below 288 GB of HBM, so the vocoder needs no
-overlap-add seams.
+overlap-add seams. Where memory must not grow with the song, or a song should share batches, convert_long cuts
+it into overlapping chunks, converts them as a ragged batch under the song's own F0 and key, and joins them with
+svc_stitch (DESIGN.md "Long-form conversion").
 """
 from dataclasses import dataclass
 
@@ -58,6 +60,16 @@ class ConvertResult:
     f0: torch.Tensor         # f64 [B, T] pitch-shifted F0
     x0: torch.Tensor         # f32 [B, T, n_mel] normalised mel from the sampler
     pcm: torch.Tensor = None  # int16 [B, T*hop + 2*(fs//20)] save_audio's samples of wav (convert(pcm16=True) only)
+
+
+@dataclass
+class LongChunks:
+    """What convert_long(return_chunks=True) adds to its waveforms; every list has one entry per song."""
+    plans: list    # audio.ChunkPlan
+    chunks: list   # lists of f32 [T_k * hop] chunk waveforms (views into the vocoder outputs)
+    shifts: list   # int32 [chunks] displacements the stitch chose (device)
+    f0: list       # f64 [T_song] the song's pitch-shifted F0, which the chunks took their slices of
+    stitched: list  # f32 [T_song * hop] the stitched song before the loudness stage and the sample conversion
 
 
 class SVCPipeline:
@@ -508,7 +520,8 @@ class SVCPipeline:
 
     def convert_ragged(self, wavs24, wavs16, singers, wavs16_float=None, fast_inference=True, speedup=10, seed=0,
                        utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None,
-                       solver=None, solver_steps=20, solver_spacing="logsnr", index_rate=None):
+                       solver=None, solver_steps=20, solver_spacing="logsnr", index_rate=None, f0_shifted=None,
+                       factor=None):
         """infer.py's sequence for B clips of different lengths as ONE padded batch: the C-ABI stages take the
         per-utterance lengths (include/svc_hip.h, "Ragged batches") and compute each clip exactly as alone.
         -> list of waveforms f32 [T_b * hop], or with pcm16=True of save_audio's samples int16
@@ -519,7 +532,11 @@ class SVCPipeline:
         clip's T_b * hop output samples against its own 24 kHz source (svc_loudness_match with both length tables),
         before the sample conversion. solver, solver_steps, solver_spacing: the sampler, as in convert().
         index_rate: feature retrieval, as in convert(): each clip's own T_b content rows against its own singer's
-        index (one svc_content_retrieve call per enrolled singer of the batch, `sel` marking that singer's clips)."""
+        index (one svc_content_retrieve call per enrolled singer of the batch, `sel` marking that singer's clips).
+        f0_shifted (None: the call as before): a list with, per clip, None or an f64 [T_b] device tensor of F0 that is
+        already pitch-shifted (a chunk's slice of its song's contour, convert_long): such a clip skips the extraction
+        and the shift, and when every clip has one no F0 kernel is launched. factor (f64 [B] on the device, needed with
+        k_step_mel="shifted" once a clip has an f0_shifted): the factor those clips' start mel is shifted by."""
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
         loudness_mix = check_loudness_mix(loudness_mix)
@@ -528,11 +545,90 @@ class SVCPipeline:
         with self.engine.lock:
             return self._convert_ragged(wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
                                         pcm16, key_shift, k_step, k_step_mel == "shifted", loudness_mix, solver_kw,
-                                        index_rate)
+                                        index_rate, f0_shifted, factor)
+
+    def convert_long(self, wavs24, wavs16, singers, wavs16_float=None, clip_s=10.0, context_s=0.64, xfade=1024,
+                     search=192, max_batch=32, return_chunks=False, fast_inference=True, speedup=10, seed=0,
+                     utt_ids=None, pcm16=False, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None,
+                     solver=None, solver_steps=20, solver_spacing="logsnr", index_rate=None):
+        """convert_ragged for songs: each is cut into overlapping chunks of clip_s seconds (audio.chunk_plan), the chunks
+        of all songs are converted as ragged batches of at most max_batch, and one svc_stitch call joins them (SOLA
+        alignment over +-search samples, a crossfade of xfade samples; DESIGN.md "Long-form conversion") -> list of
+        waveforms f32 [T_song * hop] (pcm16=True: save_audio's samples). Memory is bounded by max_batch chunks whatever
+        a song's length. In order:
+          1. the songs' F0 as a ragged batch (extract_f0, pitch_factor where k_step_mel="shifted", shift_f0): one key
+             for the whole song, and the voicing path does not restart at a cut;
+          2. the chunks through _convert_ragged, each with its slice of that F0 (f0_shifted=), its song's factor and the
+             noise id (utterance id << 12) | chunk; no loudness stage and no sample conversion here;
+          3. SVCEngine.stitch over all chunks of all songs, reading the vocoder outputs where they lie;
+          4. loudness_match (against the songs' own 24 kHz sources) and pcm16 once, on the stitched songs as a ragged
+             batch: an envelope and a peak are properties of the song.
+        A song that needs no cut is one chunk, converted as convert_ragged converts it with utterance id u << 12. The last
+        max(search - 1, 0) samples of a song of several chunks are zero (audio.chunk_plan). The other keywords are
+        convert_ragged's; utt_ids must lie in [0, 2^19). return_chunks: -> (waveforms, LongChunks)."""
+        from . import audio as A
+        k_step = self._check_k_step(k_step)
+        shifted = check_k_step_mel(k_step_mel, k_step) == "shifted"
+        loudness_mix = check_loudness_mix(loudness_mix)
+        index_rate = self._check_index_rate(index_rate)
+        solver_kw = self._solver_kw(solver, solver_steps, solver_spacing, k_step)
+        e = self.engine
+        n = len(wavs24)
+        if n < 1 or not (len(wavs16) == n == len(singers)) or (wavs16_float is not None and len(wavs16_float) != n):
+            raise ValueError("convert_long: wavs24, wavs16, singers (and wavs16_float) need one entry per song, at least one")
+        if int(max_batch) < 1:
+            raise ValueError("convert_long: max_batch >= 1")
+        ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
+        sids = [int(s) for s in singers]
+        wavs24 = [w.reshape(-1) for w in wavs24]
+        wavs16 = [w.reshape(-1) for w in wavs16]
+        w16f = None if wavs16_float is None else [w.reshape(-1) for w in wavs16_float]
+        hop = e.cfg.hop_length
+        plans = [A.chunk_plan(int(wavs24[i].shape[0]), e.cfg.fs, hop, e.cfg.n_fft, clip_s, context_s, xfade, search,
+                              utt_id=ids[i], n16=int(wavs16[i].shape[0]),
+                              n16_float=None if w16f is None else int(w16f[i].shape[0])) for i in range(n)]
+        with e.lock:
+            w24, n24 = self._pad_stack(wavs24)
+            T_s = [p.T_song for p in plans]
+            f0 = self.extract_f0(w24, max(T_s), n_samples=n24, T_b=T_s)
+            factor = e.pitch_factor(f0, *self.shift_targets(n, sids, key_shift)) if shifted else None
+            self.shift_f0(f0, sids, key_shift)
+            jobs = [(i, k) for i, p in enumerate(plans) for k in range(p.chunks)]
+            rows = []
+            for g in range(0, len(jobs), int(max_batch)):
+                grp = jobs[g:g + int(max_batch)]
+                cut = lambda ws, field: [ws[i][getattr(plans[i], field)[k][0]:getattr(plans[i], field)[k][1]] for i, k in grp]
+                fac = None if factor is None else factor[torch.tensor([i for i, _ in grp], device=factor.device)]
+                rows += self._convert_ragged(
+                    cut(wavs24, "rows24"), cut(wavs16, "rows16"), [sids[i] for i, _ in grp],
+                    None if w16f is None else cut(w16f, "rows16_float"), fast_inference, speedup, seed,
+                    [plans[i].noise_ids[k] for i, k in grp], False, 0.0, k_step, shifted, None, solver_kw, index_rate,
+                    [f0[i, plans[i].start[k]:plans[i].start[k] + plans[i].frames[k]] for i, k in grp], fac)
+            S = max(T_s) * hop
+            merged = A.merge_stitch_plans([p.stitch for p in plans], S)
+            out = torch.zeros(n, S, device=w24.device, dtype=torch.float32)
+            _, shifts = e.stitch(rows, merged, out=out, return_shifts=True)
+            n_out = [t * hop for t in T_s]
+            info = None
+            if return_chunks:
+                first = [sum(p.chunks for p in plans[:i]) for i in range(n + 1)]
+                info = LongChunks(plans, [rows[first[i]:first[i + 1]] for i in range(n)],
+                                  [shifts[first[i]:first[i + 1]] for i in range(n)], [f0[i, :T_s[i]] for i in range(n)],
+                                  [out[i, :n_out[i]].clone() for i in range(n)]
+                                  if loudness_mix is not None else [out[i, :n_out[i]] for i in range(n)])
+            if loudness_mix is not None:
+                e.loudness_match(out, w24, n_samples=n_out, src_samples=n24, mix=loudness_mix, out=out)
+            if pcm16:
+                pcm = e.pcm16(out, n_samples=n_out)
+                sil2 = pcm.shape[1] - out.shape[1]
+                wavs = [pcm[i, :n_out[i] + sil2] for i in range(n)]
+            else:
+                wavs = [out[i, :n_out[i]] for i in range(n)]
+        return (wavs, info) if return_chunks else wavs
 
     def convert_files(self, sources, singers, fast_inference=True, speedup=10, seed=0, utt_ids=None, pcm16=False,
                       float16k=None, key_shift=0.0, k_step=None, k_step_mel="source", loudness_mix=None, solver=None,
-                      solver_steps=20, solver_spacing="logsnr", index_rate=None):
+                      solver_steps=20, solver_spacing="logsnr", index_rate=None, clip_s=None, context_s=0.64):
         """convert_ragged from wav files (paths, bytes or memoryviews): audio.load_batch decodes and resamples the whole
         batch in one device stage (svc_load_pcm), then the batch is converted as convert_ragged converts it.
         float16k: the load stage also writes the float 16 kHz rows (audio.load_contentvec_audio of each file) and
@@ -540,7 +636,9 @@ class SVCPipeline:
         the configuration names a HuBERT content type (wants_float16k); False: HuBERT is fed Whisper's int16-grid rows.
         Without a HuBERT type and with None or False, load_batch is called without the keyword.
         loudness_mix: as in convert_ragged(), against the 24 kHz rows the load stage wrote.
-        solver, solver_steps, solver_spacing: the sampler, as in convert(). index_rate: as in convert_ragged()."""
+        solver, solver_steps, solver_spacing: the sampler, as in convert(). index_rate: as in convert_ragged().
+        clip_s (None: every file is one utterance, the call as before): the files are converted as convert_long
+        converts songs, in chunks of clip_s seconds with context_s seconds of context on each side."""
         from . import audio as A
         k_step = self._check_k_step(k_step)
         check_k_step_mel(k_step_mel, k_step)
@@ -552,6 +650,12 @@ class SVCPipeline:
         else:
             wavs24, wavs16 = A.load_batch(sources, self.engine.cfg.fs, self.engine)
             wavs16_float = None
+        if clip_s is not None:
+            return self.convert_long(wavs24, wavs16, singers, wavs16_float=wavs16_float, clip_s=clip_s,
+                                     context_s=context_s, fast_inference=fast_inference, speedup=speedup, seed=seed,
+                                     utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift, k_step=k_step,
+                                     k_step_mel=k_step_mel, loudness_mix=loudness_mix, index_rate=index_rate,
+                                     **solver_kw)
         return self.convert_ragged(wavs24, wavs16, singers, wavs16_float=wavs16_float, fast_inference=fast_inference,
                                    speedup=speedup, seed=seed, utt_ids=utt_ids, pcm16=pcm16, key_shift=key_shift,
                                    **({} if k_step is None else dict(k_step=k_step)),
@@ -561,7 +665,7 @@ class SVCPipeline:
 
     def _convert_ragged(self, wavs24, wavs16, singers, wavs16_float, fast_inference, speedup, seed, utt_ids,
                         pcm16=False, key_shift=0.0, k_step=None, shifted=False, loudness_mix=None, solver_kw=None,
-                        index_rate=None):
+                        index_rate=None, f0_shifted=None, factor=None):
         e = self.engine
         n = len(wavs24)
         ids = list(range(n)) if utt_ids is None else [int(u) for u in utt_ids]
@@ -574,11 +678,16 @@ class SVCPipeline:
         side.wait_stream(main)
         with torch.cuda.stream(side):
             mel, energy = e.mel_energy(w24, n_samples=n24)
-            f0 = self.extract_f0(w24, T, n_samples=n24, T_b=T_b)
-            mel_src, factor = mel, None
-            if shifted:  # as in _convert
-                factor = e.pitch_factor(f0, *self.shift_targets(n, [int(s) for s in singers], key_shift))
-            self.shift_f0(f0, [int(s) for s in singers], key_shift)
+            mel_src = mel
+            if f0_shifted is None:
+                f0 = self.extract_f0(w24, T, n_samples=n24, T_b=T_b)
+                factor = None
+                if shifted:  # as in _convert
+                    factor = e.pitch_factor(f0, *self.shift_targets(n, [int(s) for s in singers], key_shift))
+                self.shift_f0(f0, [int(s) for s in singers], key_shift)
+            else:
+                f0, factor = self._f0_supplied(w24, n24, T_b, [int(s) for s in singers], key_shift, f0_shifted, factor,
+                                               shifted)
             if shifted:
                 mel_src, info = e.mel_keyshift(w24, factor, n_samples=n24)
         content = self.ragged_content(list(wavs16), T_b, T, wavs16_float)
@@ -603,6 +712,43 @@ class SVCPipeline:
             sil2 = pcm.shape[1] - wav.shape[1]  # both silences
             return [pcm[i, :T_b[i] * hop + sil2] for i in range(n)]
         return [wav[i, :T_b[i] * hop] for i in range(n)]
+
+    def _f0_supplied(self, w24, n24, T_b, singers, key_shift, f0_shifted, factor, shifted):
+        """_convert_ragged's F0 with f0_shifted given -> (f0 f64 [B, T], the factor f64 [B] or None): a clip with an
+        entry takes it as it is (and its `factor`); the others, if any, go through extract_f0, pitch_factor and shift_f0
+        as a ragged batch of their own (each clip is computed exactly as alone, so their values are the usual ones)."""
+        e = self.engine
+        n, T = len(T_b), max(T_b)
+        if len(f0_shifted) != n:
+            raise ValueError(f"{len(f0_shifted)} f0_shifted entries for a batch of {n}")
+        have = [i for i in range(n) if f0_shifted[i] is not None]
+        need = [i for i in range(n) if f0_shifted[i] is None]
+        for i in have:
+            if f0_shifted[i].dtype != torch.float64 or tuple(f0_shifted[i].shape) != (T_b[i],):
+                raise ValueError(f"f0_shifted[{i}] must be f64 [{T_b[i]}]")
+        if shifted and have and (factor is None or factor.dtype != torch.float64 or factor.numel() != n):
+            raise ValueError(f"k_step_mel='shifted' with f0_shifted needs factor, f64 [{n}]")
+        f0 = torch.zeros(n, T, device=w24.device, dtype=torch.float64)
+        for i in have:
+            f0[i, :T_b[i]] = f0_shifted[i]
+        fac = factor.reshape(-1).clone() if shifted and have else None
+        if need:
+            ks = key_shift.tolist() if hasattr(key_shift, "tolist") else key_shift
+            ks = [float(k) for k in ks] if isinstance(ks, (list, tuple)) else [float(ks)] * n
+            Ts = max(T_b[i] for i in need)
+            sub = w24[torch.tensor(need, device=w24.device)].contiguous()
+            f0s = self.extract_f0(sub, Ts, n_samples=[n24[i] for i in need], T_b=[T_b[i] for i in need])
+            targets = self.shift_targets(len(need), [singers[i] for i in need], [ks[i] for i in need])
+            if shifted:
+                fs_ = e.pitch_factor(f0s, *targets)
+                if fac is None:
+                    fac = fs_ if len(need) == n else None
+                else:
+                    fac[torch.tensor(need, device=w24.device)] = fs_
+            e.pitch_shift(f0s, *targets)
+            for j, i in enumerate(need):
+                f0[i, :T_b[i]] = f0s[j, :T_b[i]]
+        return f0, fac
 
     def resynthesize(self, wav24, n_samples=None):
         """Copy-synthesis through the vocoder alone (how a vocoder checkpoint is judged on its own): wav24 f32 [B, N]

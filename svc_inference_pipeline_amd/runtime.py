@@ -622,6 +622,39 @@ class SVCEngine:
                   _stream())
         return (out, gain) if return_gain else out
 
+    def stitch(self, rows, plan, out=None, return_shifts=False, return_q=False):
+        """Join converted chunks into their songs on the device (svc_stitch; audio.stitch is its definition:
+        displacements and q bit-equal, crossfade samples within 1 f32 ulp, everything else copied bit for bit). rows: B
+        f32 device tensors, chunk b's waveform with at least plan.n[b] samples (views into the vocoder's output; each
+        contiguous along its samples; nothing is copied); plan: an audio.StitchPlan (host tables, in samples) -> out f32
+        [plan.out_len]. `out`: the result's tensor (f32, contiguous, plan.out_len elements of any shape); only the
+        chunks' body intervals are written, and without `out` the rest is zeros. return_shifts: also the
+        displacements int32 [B]; return_q: also q f64 [B, max(2 search, 1)]. Two launches whatever B is, on the
+        current stream; the tables are checked before any device work (SVCError)."""
+        B = len(plan.n)
+        if len(rows) != B or B < 1:
+            raise ValueError(f"stitch: {len(rows)} rows for {B} chunks")
+        for b, r in enumerate(rows):
+            if not r.is_cuda or r.dtype != torch.float32 or r.dim() != 1 or (r.numel() > 1 and r.stride(0) != 1):
+                raise ValueError(f"stitch: chunk {b}: a row must be a 1-D f32 device tensor with contiguous samples")
+            if r.numel() < int(plan.n[b]):
+                raise ValueError(f"stitch: chunk {b}: a row of {r.numel()} samples, n {int(plan.n[b])}")
+        dev = rows[0].device
+        if out is None:
+            out = torch.zeros(int(plan.out_len), device=dev, dtype=torch.float32)
+        elif out.dtype != torch.float32 or out.numel() != int(plan.out_len) or not out.is_contiguous():
+            raise ValueError(f"stitch: out must be contiguous f32 with {int(plan.out_len)} elements")
+        nc = max(2 * int(plan.search), 1)
+        shifts = torch.empty(B, device=dev, dtype=torch.int32) if return_shifts else None
+        q = torch.empty(B, nc, device=dev, dtype=torch.float64) if return_q else None
+        i64 = lambda v: (ctypes.c_int64 * B)(*[int(x) for x in v])
+        _lib.call("svc_stitch", self._ctx, (ctypes.c_void_p * B)(*[r.data_ptr() for r in rows]), B, i64(plan.n),
+                  i64(plan.lead), i64(plan.body), (ctypes.c_int32 * B)(*[int(x) for x in plan.joined]),
+                  i64(plan.out_off), int(plan.xfade), int(plan.search), float(plan.eps), _ptr(out),
+                  int(plan.out_len), _ptr(shifts), _ptr(q), _stream())
+        res = (out,) + ((shifts,) if return_shifts else ()) + ((q,) if return_q else ())
+        return res if len(res) > 1 else out
+
     def index_norms(self, x16):
         """The squared norms of a retrieval index (svc_index_norms): x16 f16 [N, D] (rows may be a column slice of a
         wider buffer: stride(0) >= D, a multiple of 8) -> f32 [N], each row's f64 sum of squares rounded to f32."""
